@@ -15,12 +15,15 @@ broadcasts them, every rank denoises its slice.  Launched either by `torch.distr
 environment) or bare as `python bench.py --gpus N`: the parent then starts the N ranks itself as child processes BEFORE
 anything touches the GPU and relays rank 0's line.
 
-Prints ONE JSON line on rank 0 (contract in the task description), with
+Prints ONE JSON line on rank 0 (contract in the task description).  A plain run sets up, warms up, times `--steps` steps,
+writes the last timed step's outputs with `--dump-outputs DIR` and prints the headline.  `--full` adds the side measurements:
   "roofline":     the kind with the largest measured time: algorithmic FLOPs (or bytes) / HIP-event time,
   "kernels":      the same per kind, each with its fraction of the MFMA (2.5 PFLOP/s bf16) or HBM (8 TB/s) peak,
   "kernels_alone_plans": the MFMA kinds of the same step under the launch-by-launch plan family (a kernel that has the chip to itself),
   "cpu_baseline": the CPU oracle (a port, NOT diffusers) timed on this box's host cores on a bounded sample,
-  "latent_rms_vs_f32": drift of the benchmarked precision against the float32 HIP path on a short fixed run.
+  "latent_rms_vs_f32": drift of the benchmarked precision against the float32 HIP path on a short fixed run,
+  "tolerance_path": the float32 pipeline timed on the full workload,
+  "graph_vs_eager_max_abs_diff": the timed path's HDR images against the instrumented eager step's.
 """
 import argparse
 import json
@@ -50,6 +53,8 @@ KIND_KERNEL = {
     "hdr_tail": "gmd_hdr_tail (denorm/clamp + u8 + Eq. 1 + /(qmax+1) + u16)",
 }
 PMC_TRAFFIC_FILE = os.path.join(ROOT, "profiles", "r05_pmc_traffic.json")
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all arrays together, under 64 MB with the .npy headers
+DUMP_SEED = 0
 
 
 def parse():
@@ -80,7 +85,43 @@ def parse():
     ap.add_argument("--cpu-threads", type=int, default=16, help="host threads of the cpu_baseline leg (a 1-GPU box owns 16 cores)")
     ap.add_argument("--cpu-baseline-only", action="store_true")
     ap.add_argument("--checksum", action="store_true", help="add sha256 of the u16 HDR codes of the last step to the line (sharding tests)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also run the side measurements after the timed steps: per-kernel timing and roofline, graph-vs-eager check, "
+                         "bf16-vs-float32 drift, float32 tolerance path, CPU baseline (each still switched off by its --no-* option)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write what the last timed step returned (HDR tail outputs and both final latents) as float32 DIR/<name>.npy; "
+                         "over 60 MB in all, the same seeded sample of every array's flattened elements; rank 0's prompts only with N>1")
+    a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    if not a.full:  # a plain run measures the headline only
+        a.no_kernel_timing = a.no_drift = a.no_tolerance_path = a.no_cpu_baseline = True
+    return a
+
+
+def dump_outputs(d, arrays):
+    """Save each device tensor of ``arrays`` as float32 ``d/<name>.npy``.  Over DUMP_BUDGET_BYTES in all, every array is
+    replaced by a sorted, seeded sample (DUMP_SEED) of the same fraction of its flattened elements: the same arguments give
+    the same indices, so two builds compare element for element."""
+    import numpy as np
+    import torch
+
+    host = {}
+    for k, v in arrays.items():
+        t = v.detach().cpu()
+        if t.dtype in (torch.bfloat16, torch.float16):
+            t = t.float()
+        host[k] = t.numpy().astype(np.float32, copy=False)
+    total = sum(x.size for x in host.values()) * 4
+    frac = min(1.0, DUMP_BUDGET_BYTES / total)
+    os.makedirs(d, exist_ok=True)
+    for k, x in host.items():
+        if frac < 1.0:
+            n = int(x.size * frac)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, n, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(d, f"{k}.npy"), x)
+    return {k: list(x.shape) for k, x in host.items()}, frac
 
 
 # ------------------------------------------------------------------------------------------------
@@ -268,9 +309,13 @@ def main():
     # parameters) right after the timed region, with torch.cuda.Event pairs on the launch stream around every launch.
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        out, _, _ = step()
+        out, sdr_last, gm_last = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if a.dump_outputs and rank == 0:
+        shapes, frac = dump_outputs(a.dump_outputs, {**out, "sdr_latent": sdr_last, "gm_latent": gm_last})
+        print(f"[bench] wrote {len(shapes)} arrays to {a.dump_outputs}" + (f" (seeded sample: {frac:.3f} of each)" if frac < 1.0 else ""),
+              file=sys.stderr)
     timer = None
     timer_alone = None
     path_diff = None

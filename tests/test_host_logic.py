@@ -39,6 +39,17 @@ def unets():
     return fixtures.build_unet("tiny", 4), fixtures.build_unet("tiny", 8)
 
 
+# The golden vectors were written by the oracle on one host.  The host's CPU kernels (thread count, instruction set) move the last
+# bits of these loops: up to 4.3e-5 (|x| <= 37) between 1 and 8 threads, or AVX2 and AVX-512 kernels.  Bit identity is therefore
+# asserted against the oracle run live on the same host, and the stored vectors pin the oracle itself to GOLDEN_ATOL.
+GOLDEN_ATOL = 5e-4
+
+
+def assert_oracle_bits(got, live, golden):
+    assert torch.equal(got, live)  # same torch expressions on the same host -> bit identical
+    assert torch.allclose(live, torch.from_numpy(golden), rtol=0.0, atol=GOLDEN_ATOL)
+
+
 def test_pndm_product_equals_oracle_bitwise():
     p, o = PNDMScheduler(**SD_PNDM), OS.PNDMScheduler()
     for n in (50, 10, 7):
@@ -147,7 +158,9 @@ def test_gm_pipeline_generic_path_matches_golden(unets, golden_dir):
             num_inference_steps=10, guidance_scale=7.5, output_type="latent", noise_level=0.0,  # unknown kwargs are ignored
             callback_on_step_end=lambda pipe, i, t, kw: (seen.append(i) or {}))
     assert isinstance(out, StableDiffusionPipelineOutput) and out.nsfw_content_detected is None
-    assert torch.equal(out.images, torch.from_numpy(g["out"]))  # same torch expressions on the same host -> bit identical
+    live = OP.gm_loop(unets[1], OS.PNDMScheduler(), torch.from_numpy(g["sdr_latent"]), torch.from_numpy(g["prompt_embeds"]),
+                      torch.from_numpy(g["negative_prompt_embeds"]), torch.from_numpy(g["latents"]), num_inference_steps=10, guidance_scale=7.5)
+    assert_oracle_bits(out.images, live, g["out"])
     assert seen == list(range(11)) and p.num_timesteps == 11
     assert out[0] is out.images
     tup = p(torch.from_numpy(g["sdr_latent"]), prompt_embeds=torch.from_numpy(g["prompt_embeds"]),
@@ -173,6 +186,8 @@ def test_gm_pipeline_callback_can_replace_latents_and_interrupt(unets):
 
 def test_dual_pipeline_generic_path_matches_golden(unets, golden_dir):
     g = np.load(os.path.join(golden_dir, "pipeline_oracle_dual_tiny.npz"))
+    live = OP.dual_loop(unets[0], unets[1], OS.PNDMScheduler(), torch.from_numpy(g["prompt_embeds"]), torch.from_numpy(g["negative_prompt_embeds"]),
+                        torch.from_numpy(g["latents"]), num_inference_steps=10, guidance_scale=7.5)
     for cls in (StableDiffusionDualUNetPipeline, StableDiffusionDualUNetImprovedPipeline):
         p = dual_pipe(*unets, cls=cls)
         p.set_progress_bar_config(disable=True)
@@ -180,7 +195,8 @@ def test_dual_pipeline_generic_path_matches_golden(unets, golden_dir):
                 latents=torch.from_numpy(g["latents"]), height=128, width=128, num_inference_steps=10, guidance_scale=7.5,
                 output_type="latent", return_dict=True)  # return_dict is ignored: always the bare tuple (dual.py:1132)
         assert isinstance(out, tuple) and len(out) == 2
-        assert torch.equal(out[0], torch.from_numpy(g["sdr_out"])) and torch.equal(out[1], torch.from_numpy(g["gm_out"]))
+        assert_oracle_bits(out[0], live[0], g["sdr_out"])
+        assert_oracle_bits(out[1], live[1], g["gm_out"])
         assert p.gm_scheduler is not p.scheduler and p.gm_scheduler.counter == p.scheduler.counter == 11
 
 
@@ -191,7 +207,10 @@ def test_dual_pipeline_rescale_and_no_cfg(unets, golden_dir):
     a, b = p(prompt_embeds=torch.from_numpy(g["prompt_embeds"]), negative_prompt_embeds=torch.from_numpy(g["negative_prompt_embeds"]),
              latents=torch.from_numpy(g["latents"]), height=128, width=128, num_inference_steps=6, guidance_scale=5.0,
              guidance_rescale=0.7, output_type="latent")
-    assert torch.equal(a, torch.from_numpy(g["sdr_out"])) and torch.equal(b, torch.from_numpy(g["gm_out"]))
+    la, lb = OP.dual_loop(unets[0], unets[1], OS.PNDMScheduler(), torch.from_numpy(g["prompt_embeds"]), torch.from_numpy(g["negative_prompt_embeds"]),
+                          torch.from_numpy(g["latents"]), num_inference_steps=6, guidance_scale=5.0, guidance_rescale=0.7)
+    assert_oracle_bits(a, la, g["sdr_out"])
+    assert_oracle_bits(b, lb, g["gm_out"])
     # guidance_scale <= 1: no CFG, the GM UNet receives the same (only) embeddings -- works, unlike the reference's [1:] slice
     pe = torch.from_numpy(g["prompt_embeds"])
     a1, b1 = p(prompt_embeds=pe, latents=torch.from_numpy(g["latents"]), height=128, width=128, num_inference_steps=3,
