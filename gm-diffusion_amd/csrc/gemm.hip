@@ -14,7 +14,7 @@
 //   * gemm_f32_kernel : exact float32 FMA path used for parity runs (64x64x16 tiles, 4x4 per thread).
 //
 // For conv3x3 the GEMM row m is the output pixel (b, oy, ox), k = (ky*3+kx)*Cin + c; the A tile is
-// gathered on the fly (zero padding, stride 2, fused nearest-2x upsample) -- no im2col buffer.
+// gathered on the fly (zero padding, stride 2, fused nearest upsample to 2x or to a given size) -- no im2col buffer.
 #include "gemm_shared.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -2941,10 +2941,23 @@ struct GnTail {
     int silu;
 };
 
-void conv_out_shape(int Hin, int Win, int stride, int upsample, int pad_mode, int& Hout, int& Wout, int& pad_lo) {
-    if (upsample) { Hout = 2 * Hin; Wout = 2 * Win; pad_lo = 1; }
+// `upsample`: 0, 1 (nearest 2x) or GMD_UPSAMPLE_TO(Hout, Wout) (nearest to a given size; include/gmd_hip.h).  False (message left
+// for the caller's error) when the requested size is not one a stride-2 level can have come from: Hout in {2 Hin - 1, 2 Hin}.  For
+// those two torch's nearest map with size= is dst >> 1, as for 2x: only the bound of the virtual image moves (the kernels test
+// uy >= Hout), and Hout <= 2 Hin keeps uy >> 1 inside the source.  `upsample` leaves as 0 / 1.
+bool conv_out_shape(int Hin, int Win, int stride, int& upsample, int pad_mode, int& Hout, int& Wout, int& pad_lo) {
+    if (upsample == 1) { Hout = 2 * Hin; Wout = 2 * Win; pad_lo = 1; }
+    else if (upsample) {
+        Hout = upsample >> 16; Wout = upsample & 0xFFFF; pad_lo = 1;
+        if (upsample < 0 || !(Hout == 2 * (int64_t)Hin - 1 || Hout == 2 * (int64_t)Hin) || !(Wout == 2 * (int64_t)Win - 1 || Wout == 2 * (int64_t)Win)) {
+            gmd_set_error("gmd_conv3x3: upsample to %dx%d from %dx%d: each output side must be 2*in - 1 or 2*in", Hout, Wout, Hin, Win);
+            return false;
+        }
+        upsample = 1;
+    }
     else if (pad_mode == 1) { Hout = (Hin + 1 - 3) / 2 + 1; Wout = (Win + 1 - 3) / 2 + 1; pad_lo = 0; }
     else { Hout = (Hin + 2 - 3) / stride + 1; Wout = (Win + 2 - 3) / stride + 1; pad_lo = 1; }
+    return true;
 }
 
 // split-K factor the conv launch will use (1 = unsplit); the same planners the launch itself calls
@@ -2967,14 +2980,14 @@ int conv3x3_impl(const void* X, const void* Wt, void* Y, int dtype, int out_dtyp
     GMD_REQUIRE(stride == 1 || stride == 2, "gmd_conv3x3: stride must be 1 or 2");
     GMD_REQUIRE(!(upsample && stride != 1), "gmd_conv3x3: upsample requires stride 1");
     GMD_REQUIRE(pad_mode == 0 || (pad_mode == 1 && stride == 2 && !upsample), "gmd_conv3x3: pad_mode 1 requires stride 2");
+    int Hout, Wout, pad_lo;
+    if (!conv_out_shape(Hin, Win, stride, upsample, pad_mode, Hout, Wout, pad_lo)) return GMD_ERR_INVALID;
     const int kmul = is16 ? 64 : split ? 32 : 16;
     GMD_REQUIRE(Cin % kmul == 0, "gmd_conv3x3: Cin=%d must be a multiple of %d (pad the channels)", Cin, kmul);
     GMD_REQUIRE(X && Wt && (Y || gn) && gmd_aligned16(X) && gmd_aligned16(Wt) && gmd_aligned16(Y), "gmd_conv3x3: null or unaligned pointer");
     GMD_REQUIRE(bias == nullptr || gmd_aligned16(bias), "gmd_conv3x3: bias must be 16-byte aligned (it is read with float4 loads)");
     GMD_REQUIRE(residual == nullptr || gmd_aligned16(residual), "gmd_conv3x3: unaligned residual");
     GMD_REQUIRE(residual == nullptr || out_dtype == dtype || !is16, "gmd_conv3x3: residual needs out_dtype == dtype");
-    int Hout, Wout, pad_lo;
-    conv_out_shape(Hin, Win, stride, upsample, pad_mode, Hout, Wout, pad_lo);
     const int64_t M = (int64_t)B * Hout * Wout;
     GMD_REQUIRE(M < (1LL << 31), "gmd_conv3x3: too many output pixels");
     GemmParams p{};
@@ -3027,7 +3040,7 @@ int gmd_conv3x3_gn_fusable(int dtype, int B, int Hin, int Win, int Cin, int Cout
     if (!(gmd_is_half(dtype) || split) || B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || groups <= 0) return 0;
     if (!(stride == 1 || stride == 2) || (upsample && stride != 1) || !(pad_mode == 0 || (pad_mode == 1 && stride == 2 && !upsample))) return 0;
     int Hout, Wout, pad_lo;
-    conv_out_shape(Hin, Win, stride, upsample, pad_mode, Hout, Wout, pad_lo);
+    if (!conv_out_shape(Hin, Win, stride, upsample, pad_mode, Hout, Wout, pad_lo)) return 0;
     const int64_t M = (int64_t)B * Hout * Wout;
     if (M >= (1LL << 31) || Cin % (split ? 32 : 64)) return 0;
     // one workgroup per (sample, group) walks all slabs of its slice: below one workgroup per CU the separate, fully parallel

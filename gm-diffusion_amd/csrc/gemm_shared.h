@@ -110,7 +110,7 @@ __device__ __forceinline__ int64_t a_offset(const GemmParams& p, const RowCtx& r
     int iy, ix;
     if (p.upsample) {
         const int uy = r.oy + ky - 1, ux = r.ox + kx - 1;
-        if (uy < 0 || ux < 0 || uy >= 2 * p.Hin || ux >= 2 * p.Win) return -1;
+        if (uy < 0 || ux < 0 || uy >= p.Hout || ux >= p.Wout) return -1;  // Hout in {2 Hin - 1, 2 Hin} (host-checked): uy >> 1 < Hin
         iy = uy >> 1;
         ix = ux >> 1;
     } else {
@@ -217,7 +217,7 @@ __device__ __forceinline__ unsigned conv_tap_offset(const GemmParams& p, bool va
     int iy, ix;
     if (p.upsample) {
         const int uy = oy + ky - 1, ux = ox + kx - 1;
-        if (uy < 0 || ux < 0 || uy >= 2 * p.Hin || ux >= 2 * p.Win) return kOOB;
+        if (uy < 0 || ux < 0 || uy >= p.Hout || ux >= p.Wout) return kOOB;  // Hout in {2 Hin - 1, 2 Hin} (host-checked): uy >> 1 < Hin
         iy = uy >> 1;
         ix = ux >> 1;
     } else {

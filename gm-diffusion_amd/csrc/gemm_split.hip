@@ -44,7 +44,7 @@ __device__ __forceinline__ unsigned conv_tap_offset_f32(const GemmParams& p, boo
     int iy, ix;
     if (p.upsample) {
         const int uy = oy + ky - 1, ux = ox + kx - 1;
-        if (uy < 0 || ux < 0 || uy >= 2 * p.Hin || ux >= 2 * p.Win) return kOOB;
+        if (uy < 0 || ux < 0 || uy >= p.Hout || ux >= p.Wout) return kOOB;  // Hout in {2 Hin - 1, 2 Hin} (host-checked): uy >> 1 < Hin
         iy = uy >> 1;
         ix = ux >> 1;
     } else {

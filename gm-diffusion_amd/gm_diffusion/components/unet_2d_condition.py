@@ -195,6 +195,9 @@ class _HipModule(ConfigMixin):
         return self._f32(self._raw[key + ".weight"]), self._f32(self._raw[key + ".bias"])
 
 
+SCORE_CHUNK_BYTES = 1 << 30  # composed_attention: float32 score matrix held at once (16,384^2 tokens = exactly this)
+
+
 def composed_attention(q, q_col, ldq, k, k_col, ldk, vt, B, H, d, nq, nk, scale, dtype, causal=False):
     """Attention as GEMM -> row softmax -> GEMM (float32 parity path and the d=512 VAE block).
     q/k: buffers with rows of ldq/ldk elements, head h at columns q_col + h*d; vt: [B, H*d, ldvt] with
@@ -206,15 +209,27 @@ def composed_attention(q, q_col, ldq, k, k_col, ldk, vt, B, H, d, nq, nk, scale,
     if ldvt < nkp:
         raise HipExtensionError("composed_attention: vt row stride too small")
     out = torch.empty((B, nq, H * d), dtype=dtype, device=q.device)
-    s = torch.empty((H, nq, nkp), dtype=torch.float32, device=q.device)
+    # the float32 scores of all heads for `rows` query rows at a time: the whole [H, nq, nkp] matrix while it stays within
+    # SCORE_CHUNK_BYTES (every size up to the VAE's 16,384 tokens of a 1024 x 1024 image: one pass, as before); beyond that
+    # (1920 x 1080: 32,400 tokens, 4.2 GB of scores, more than one raw buffer descriptor addresses) the query rows are walked in
+    # chunks -- a row's softmax needs only its own scores, so each chunk is a complete attention over all keys
+    rows = nq
+    if H * nq * nkp * 4 > SCORE_CHUNK_BYTES:
+        rows = max(256, SCORE_CHUNK_BYTES // (H * nkp * 4) // 256 * 256)
+        if causal:
+            raise HipExtensionError("composed_attention: a causal mask over chunked query rows is not implemented")
+    s = torch.empty((H, min(rows, nq), nkp), dtype=torch.float32, device=q.device)
     for b in range(B):
-        ops.gemm_raw(q.data_ptr() + (b * nq * ldq + q_col) * es, k.data_ptr() + (b * nk * ldk + k_col) * es, s.data_ptr(),
-                     dtype, torch.float32, nq, nk, d, ldq, ldk, nkp, batch=H, sA=d, sW=d, sC=nq * nkp)
-        p = ops.softmax_rows(s, nk, scale, dtype, ldp=nkp, causal_nq=nq if causal else 0)
-        # float32: the probabilities (~1/nk) would lose their float16 lo half to the subnormal range in a split product, so
-        # this one stays on the exact kernel (small: the VAE mid block and the 77-token text encoder only)
-        ops.gemm_raw(p.data_ptr(), vt.data_ptr() + b * H * d * ldvt * es, out.data_ptr() + b * nq * H * d * es,
-                     dtype, dtype, nq, d, nkp, nkp, ldvt, H * d, batch=H, sA=nq * nkp, sW=d * ldvt, sC=d, exact=True)
+        for r0 in range(0, nq, rows):
+            nr = min(rows, nq - r0)
+            sc = s if nr == s.shape[1] else s.view(-1)[:H * nr * nkp].view(H, nr, nkp)
+            ops.gemm_raw(q.data_ptr() + ((b * nq + r0) * ldq + q_col) * es, k.data_ptr() + (b * nk * ldk + k_col) * es, sc.data_ptr(),
+                         dtype, torch.float32, nr, nk, d, ldq, ldk, nkp, batch=H, sA=d, sW=d, sC=nr * nkp)
+            p = ops.softmax_rows(sc, nk, scale, dtype, ldp=nkp, causal_nq=nq if causal else 0)
+            # float32: the probabilities (~1/nk) would lose their float16 lo half to the subnormal range in a split product, so
+            # this one stays on the exact kernel (small: the VAE mid block and the 77-token text encoder only)
+            ops.gemm_raw(p.data_ptr(), vt.data_ptr() + b * H * d * ldvt * es, out.data_ptr() + (b * nq + r0) * H * d * es,
+                         dtype, dtype, nr, d, nkp, nkp, ldvt, H * d, batch=H, sA=nr * nkp, sW=d * ldvt, sC=d, exact=True)
     return out
 
 
@@ -779,7 +794,7 @@ class UNet2DConditionModel(_HipModule):
                 skips.append((x, H, W))
             if "ds" in blk:
                 x, H, W = ops.conv3x3(x, blk["ds"][0], B, H, W, bias=blk["ds"][1], stride=2,
-                                      colstats=self._wants_colstats(H // 2, W // 2))
+                                      colstats=self._wants_colstats((H + 1) // 2, (W + 1) // 2))  # stride 2, padding 1: ceil
                 skips.append((x, H, W))
             mark()  # end of a down block
         x = self._resnet(w["mid"]["r0"], x, B, H, W, temb, eps)
@@ -793,8 +808,11 @@ class UNet2DConditionModel(_HipModule):
                 if "attn" in blk:
                     x = self._transformer(blk["attn"][j], x, B, H, W, ehs)
             if "us" in blk:
-                x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], upsample=True,
-                                      colstats=self._wants_colstats(2 * H, 2 * W))
+                # upsample to the size of the skip this level's output meets next (diffusers: upsample_size =
+                # down_block_res_samples[-1].shape[2:]): 2H x 2W -- then the very launch of upsample=True -- unless the stride-2
+                # convolution on the way down halved an odd side
+                ho, wo = skips[-1][1:]
+                x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], out_size=(ho, wo), colstats=self._wants_colstats(ho, wo))
             mark()  # end of an up block
         x = ops.groupnorm(x, B, c.norm_num_groups, w["norm_out"][0], w["norm_out"][1], eps, silu=True, split_out=self._sa(w["conv_out"][0]))
         y, _, _ = ops.conv3x3(x, w["conv_out"][0], B, H, W, bias=w["conv_out"][1], out_dtype=torch.float32)
@@ -883,8 +901,6 @@ class UNet2DConditionModel(_HipModule):
         self._ensure()
         first = sample[0] if isinstance(sample, (tuple, list)) else sample
         B, _, H, W = first.shape
-        if H % (2 ** (len(self.config.block_out_channels) - 1)) or W % (2 ** (len(self.config.block_out_channels) - 1)):
-            raise ValueError(f"latent size {H}x{W} must be divisible by {2 ** (len(self.config.block_out_channels) - 1)}")
         x = self.pack_input(sample)
         ehs = self.prepare_context(encoder_hidden_states)
         if ehs.shape[0] != B:

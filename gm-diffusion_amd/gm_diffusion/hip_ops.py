@@ -509,15 +509,32 @@ def ff_geglu_fused(x, w1i, b1i, w2, b2, residual):
     return y
 
 
+def upsample_code(H, W, out_size):
+    """The ``upsample`` argument of the C ABI for nearest upsampling of an H x W map to ``out_size`` = (Hout, Wout), each side
+    ``2 * in - 1`` or ``2 * in`` (GMD_UPSAMPLE_TO of include/gmd_hip.h; exactly 2x is the plain ``1``, the launch of ``upsample=True``)."""
+    ho, wo = (int(v) for v in out_size)
+    if ho not in (2 * H - 1, 2 * H) or wo not in (2 * W - 1, 2 * W) or ho < 1 or wo < 1 or ho >= 1 << 15 or wo >= 1 << 16:
+        raise HipExtensionError(f"conv3x3: out_size {ho}x{wo} from {H}x{W}: each side must be 2*in - 1 or 2*in")
+    return 1 if (ho, wo) == (2 * H, 2 * W) else (ho << 16) | wo
+
+
 def conv3x3(x, w, B, H, W, bias=None, rowbias=None, residual=None, stride=1, upsample=False, pad_mode=0, out_dtype=None,
-            colstats=False, x_split=False):
-    """x: [B, H*W, Cin]; w: [Cout, 9*Cin] (tap-major); returns ([B, Hout*Wout, Cout], Hout, Wout)."""
+            colstats=False, x_split=False, out_size=None):
+    """x: [B, H*W, Cin]; w: [Cout, 9*Cin] (tap-major); returns ([B, Hout*Wout, Cout], Hout, Wout).  ``upsample=True`` convolves the
+    nearest-2x image; ``out_size=(Hout, Wout)`` the nearest-upsampled image of that size (diffusers' ``Upsample2D(x, output_size)``;
+    each side ``2 * in - 1`` or ``2 * in``)."""
     _dev(x, w, bias, residual)
     rb_ptr, rb_ld = _rowbias(rowbias)
     cin, cout = x.shape[-1], w.shape[0]
     if x.numel() != B * H * W * cin or w.shape[1] != 9 * cin or x.dtype != w.dtype:
         raise HipExtensionError(f"conv3x3: shape/dtype mismatch x={tuple(x.shape)} w={tuple(w.shape)} B,H,W={B},{H},{W}")
-    if upsample:
+    up = int(bool(upsample))
+    if out_size is not None:
+        if stride != 1 or pad_mode != 0:
+            raise HipExtensionError("conv3x3: out_size is the upsampling convolution's (stride 1, pad_mode 0)")
+        up = upsample_code(H, W, out_size)
+        ho, wo = int(out_size[0]), int(out_size[1])
+    elif upsample:
         ho, wo = 2 * H, 2 * W
     elif pad_mode == 1:
         ho, wo = (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1
@@ -537,7 +554,7 @@ def conv3x3(x, w, B, H, W, bias=None, rowbias=None, residual=None, stride=1, ups
     tm = tm if tm is not None and tm.wants("conv3x3") else None
     t0 = tm.begin() if tm else None
     check(lib().gmd_conv3x3(_ptr(x), _ptr(w), _ptr(y), code, dtype_code(out_dtype), B, H, W, cin, cout,
-                            stride, int(upsample), pad_mode, _ptr(_f32(bias, "bias")), rb_ptr, rb_ld,
+                            stride, up, pad_mode, _ptr(_f32(bias, "bias")), rb_ptr, rb_ld,
                             _ptr(residual), float(getattr(w, "_alpha", 1.0)), _ptr(st), COLSTATS_BUCKET if st is not None else 0,
                             _ptr(ws), WORKSPACE_BYTES, _stream()), "gmd_conv3x3")
     if tm:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GMD_ABI_VERSION 11
+#define GMD_ABI_VERSION 12
 #define GMD_WS_TAIL_BYTES 65536 /* see "WORKSPACE CONTRACT" at gmd_gemm_nt */
 
 #define GMD_OK 0
@@ -304,8 +304,17 @@ int gmd_ff_geglu_fused(const void* X, const void* W1i, const float* b1i, const v
  * stride 1 or 2 (Downsample2D: Hout = (Hin+2-3)/2+1); upsample=1 fuses nearest-2x
  * (Upsample2D: conv over the virtual 2Hin x 2Win image).  pad_mode 0: symmetric padding 1;
  * pad_mode 1: pad (0,1,0,1) then stride 2 (VAE encoder Downsample2D(padding=0)).
+ * upsample = GMD_UPSAMPLE_TO(Hout, Wout) (ABI v12) fuses nearest upsampling to a GIVEN size, each side 2*in - 1 or 2*in: diffusers'
+ * Upsample2D.forward(hidden_states, output_size) = conv(F.interpolate(hidden_states, size=output_size, mode="nearest")), which
+ * UNet2DConditionModel takes (upsample_size = down_block_res_samples[-1].shape[2:]) when a latent side is not a multiple of
+ * 2 ** (levels - 1): a stride-2 level maps H -> ceil(H / 2), so the way back up meets a skip of 2 Hin - 1 or 2 Hin rows.  For
+ * exactly those sizes torch's nearest map is src = dst >> 1, the 2x map with the virtual image cut at Hout x Wout
+ * (tests/test_anysize_cpu.py pins that to F.interpolate); GMD_UPSAMPLE_TO(2 Hin, 2 Win) is the launch of upsample=1.  Any other
+ * size, and any other value of `upsample` above 1 or below 0, returns GMD_ERR_INVALID before a launch.  The same values hold for
+ * gmd_conv3x3_gn_fusable (which answers 0) and gmd_conv3x3_groupnorm.
  * Epilogue as gmd_gemm_nt (rowbias is [B, ldrb], one row per sample; alpha scales the
  * accumulated sum before the bias: 1 for a plain convolution, 2^-s for a weight that was stored scaled by 2^s).  Cin % 64 == 0 (BF16 / F16), % 32 (F32S / F32SW), % 16 (F32). */
+#define GMD_UPSAMPLE_TO(Hout, Wout) (((int)(Hout) << 16) | (int)(Wout)) /* 1 <= Hout < 32768, 1 <= Wout < 65536 */
 int gmd_conv3x3(const void* X, const void* Wt, void* Y, int dtype, int out_dtype,
                 int B, int Hin, int Win, int Cin, int Cout, int stride, int upsample, int pad_mode,
                 const float* bias, const float* rowbias, int64_t ldrb, const void* residual, float alpha,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python
 """Interleaved A/B of bench.py variants on ONE box (the boxes differ by 1-2 %, so variants must be compared inside one lease):
 each variant is an environment setting `NAME=VALUE[,NAME=VALUE...]`; the variants are run round-robin for `--rounds` rounds as
-child processes and the per-variant ms_per_step values are printed with their median.
+child processes and the per-variant ms_per_step values are printed with their median.  The pseudo-setting `TREE=DIR` runs DIR/bench.py
+(another checkout of the project, built in place, e.g. the parent commit) instead of this tree's: A/B of two commits.
 Usage: ab_bench.py [--rounds 3] [--steps 6] [--args "--no-overlap"] VAR1 VAR2 ...   (a variant "-" = no extra environment)"""
 import argparse, json, os, statistics, subprocess, sys
 
@@ -17,13 +18,17 @@ res = {v: [] for v in a.variants}
 for r in range(a.rounds):
     for v in a.variants:
         env = dict(os.environ)
+        tree = ROOT
         if v != "-":
             for kv in v.split(","):
                 k, val = kv.split("=", 1)
-                env[k] = val
-        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-drift",
+                if k == "TREE":
+                    tree = os.path.abspath(val)
+                else:
+                    env[k] = val
+        cmd = [sys.executable, os.path.join(tree, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-drift",
                "--no-tolerance-path", "--no-kernel-timing"] + a.args.split()
-        out = subprocess.run(cmd, env=env, capture_output=True, text=True).stdout
+        out = subprocess.run(cmd, env=env, cwd=tree if tree != ROOT else None, capture_output=True, text=True).stdout
         line = [l for l in out.splitlines() if l.startswith("{")]
         ms = json.loads(line[-1])["ms_per_step"] if line else float("nan")
         res[v].append(ms)
