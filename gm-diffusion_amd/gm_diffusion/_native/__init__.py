@@ -14,7 +14,7 @@ from ctypes import c_char_p, c_float, c_int, c_int64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("GMD_LIB_OVERRIDE") or os.path.join(_HERE, "libgmd_hip.so")  # override: kernel-debug builds only
-ABI_VERSION = 12
+ABI_VERSION = 13
 
 GMD_F32, GMD_BF16, GMD_F16, GMD_F32S, GMD_F32SW, GMD_F32SA = 0, 1, 2, 3, 4, 5
 ACT_NONE, ACT_SILU, ACT_GEGLU, ACT_QUICK_GELU = 0, 1, 2, 3
@@ -26,6 +26,8 @@ SIGNATURES = {
     "gmd_abi_version": [],
     "gmd_last_error": [],
     "gmd_hdr_tail": [P, P, I, I, I, I, I, F, F, I, P, P, P, P, P, P, P, P],
+    "gmd_hdr_tail_resized": [P, I, I, P, I, I, I, I, I, I, I, F, F, I, P, P, P, P, P, P, P, P, P],
+    "gmd_prepare_sdr": [P, I, I, I, P, I, I, I, I, I, P],
     "gmd_apply_gm_to_sdr": [P, P, P, L, F, F, I, P],
     "gmd_tmo": [P, P, L, I, F, F, P],
     "gmd_gamut_compress": [P, P, I, L, P],

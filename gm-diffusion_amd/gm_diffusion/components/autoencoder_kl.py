@@ -282,7 +282,27 @@ class AutoencoderKL(_HipModule):
         if x.dtype != torch.float32:
             x = ops.cast(x.contiguous(), torch.float32)
         B, _, H, W = x.shape
-        h = ops.pack_unet_input(x.contiguous(), None, 1, self._img_pad, self._dtype)
+        return self.encode_nhwc(ops.pack_unet_input(x.contiguous(), None, 1, self._img_pad, self._dtype), H, W, return_dict)
+
+    def encoder_input_spec(self):
+        """(channels, dtype) of the channels-last tensor ``encode_nhwc`` takes: what ``hip_ops.prepare_sdr(layout="nhwc")`` writes."""
+        self._ensure()
+        if not self.with_encoder:
+            raise RuntimeError("this AutoencoderKL was loaded without encoder weights")
+        return self._img_pad, self._dtype
+
+    @_in_own_f32_mode
+    def encode_nhwc(self, h, H, W, return_dict=True):
+        """``encode`` from the packed input it builds itself: h [B, H*W, cp] channels-last in the model's dtype, image in [-1,1] in
+        channels 0..2 and zeros in the padding channels (``encoder_input_spec``)."""
+        self._ensure()
+        if not self.with_encoder:
+            raise RuntimeError("this AutoencoderKL was loaded without encoder weights")
+        w = self._w
+        c = self.config
+        B = h.shape[0]
+        if h.dim() != 3 or h.shape[1] != H * W or h.shape[2] != self._img_pad or h.dtype != self._dtype:
+            raise ValueError(f"encode_nhwc expects [{B}, {H * W}, {self._img_pad}] {self._dtype}, got {tuple(h.shape)} {h.dtype}")
         h, _, _ = ops.conv3x3(h, w["e_in"][0], B, H, W, bias=w["e_in"][1])
         for blk in w["e_down"]:
             for r in blk["res"]:

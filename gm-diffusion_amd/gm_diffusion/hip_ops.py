@@ -25,7 +25,7 @@ from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GM
 __all__ = [
     "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "ddpm_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
-    "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail",
+    "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
 ]
 
@@ -1067,6 +1067,81 @@ def hdr_tail(sdr_dec, gm_dec, layout, B, H, W, qmax=99.0, eps=1 / 64, clamp=Fals
     if tm:  # 2 x 3 float32 read per pixel + every requested output written once
         px = B * H * W
         tm.end("hdr_tail", 0.0, px * 2 * 3 * sdr_dec.element_size() + sum(v.numel() * v.element_size() for v in out.values()), t0)
+    return out
+
+
+_TAIL_KINDS = {"sdr": torch.float32, "gm": torch.float32, "sdr_u8": torch.uint8, "gm_u8": torch.uint8,
+               "hdr": torch.float32, "hdr_file": torch.float32, "hdr_u16": torch.uint16, "hdr_rgbe": torch.uint8}
+
+
+def _operand_hw(t, layout, hw, name):
+    """(h, w) of a tail operand: read off a [B,3,h,w] tensor, given by the caller for the flattened channels-last layouts."""
+    if layout == 0 and t.dim() == 4:
+        h, w = int(t.shape[2]), int(t.shape[3])
+        if hw is not None and tuple(hw) != (h, w):
+            raise HipExtensionError(f"hdr_tail_resized: {name}_hw={tuple(hw)} but the tensor is {h}x{w}")
+        return h, w
+    if hw is None:
+        raise HipExtensionError(f"hdr_tail_resized: {name}_hw is needed for layout {layout}")
+    h, w = int(hw[0]), int(hw[1])
+    ch = (3, 3, 4)[layout]
+    if t.numel() != t.shape[0] * h * w * ch:
+        raise HipExtensionError(f"hdr_tail_resized: {name} has {t.numel()} elements, expected B x {h} x {w} x {ch}")
+    return h, w
+
+
+def hdr_tail_resized(sdr, gm_dec, layout, out_size, sdr_hw=None, gm_hw=None, qmax=99.0, eps=1 / 64, clamp=False, source_u8=False,
+                     want=("sdr", "gm", "sdr_u8", "gm_u8", "hdr", "hdr_file", "hdr_u16", "hdr_rgbe")):
+    """The fused tail at ``out_size`` = (H, W): both operands (layouts of ``hdr_tail``; ``sdr_hw`` / ``gm_hw`` give the sizes of
+    flattened channels-last operands) are bilinearly resampled onto it inside the kernel (gmd_hdr_tail_resized).  ``source_u8``: ``sdr``
+    is a uint8 [B,H,W,3] picture already at the output size.  Returns a dict of [B,H,W,3] tensors (``hdr_rgbe``: [B,H,W,4] uint8)."""
+    _dev(sdr, gm_dec)
+    H, W = int(out_size[0]), int(out_size[1])
+    B = gm_dec.shape[0]
+    if source_u8:
+        if sdr.dtype != torch.uint8 or tuple(sdr.shape) != (B, H, W, 3):
+            raise HipExtensionError(f"hdr_tail_resized: source_u8 expects a uint8 [{B}, {H}, {W}, 3] picture, got {sdr.dtype} {tuple(sdr.shape)}")
+        hs, ws = H, W
+    else:
+        if sdr.dtype != gm_dec.dtype:
+            raise HipExtensionError("hdr_tail_resized: dtype mismatch")
+        if sdr.shape[0] != B:
+            raise HipExtensionError("hdr_tail_resized: batch mismatch")
+        hs, ws = _operand_hw(sdr, layout, sdr_hw, "sdr")
+    hg, wg = _operand_hw(gm_dec, layout, gm_hw, "gm")
+    unknown = [k for k in want if k not in _TAIL_KINDS]
+    if unknown:
+        raise HipExtensionError(f"hdr_tail_resized: unknown outputs {unknown}")
+    dev = gm_dec.device
+    out = {k: torch.empty((B, H, W, 4 if k == "hdr_rgbe" else 3), dtype=_TAIL_KINDS[k], device=dev) for k in want}
+    g = lambda k: _ptr(out.get(k))
+    tm, t0 = _timed("hdr_tail_resized")
+    check(lib().gmd_hdr_tail_resized(_ptr(sdr), hs, ws, _ptr(gm_dec), hg, wg, dtype_code(gm_dec.dtype), layout, B, H, W, float(qmax),
+                                     float(eps), (1 if clamp else 0) | (2 if source_u8 else 0), g("sdr"), g("gm"), g("sdr_u8"),
+                                     g("gm_u8"), g("hdr"), g("hdr_file"), g("hdr_u16"), g("hdr_rgbe"), _stream()), "gmd_hdr_tail_resized")
+    if tm:  # the operands are read once from HBM (the four taps of neighbouring pixels hit the caches) + every requested output written once
+        rd = B * 3 * (hg * wg * gm_dec.element_size() + hs * ws * sdr.element_size())
+        tm.end("hdr_tail_resized", 0.0, rd + sum(v.numel() * v.element_size() for v in out.values()), t0)
+    return out
+
+
+def prepare_sdr(images_u8, size, dtype=torch.float32, layout="nchw", cp=8):
+    """uint8 [B,h,w,3] pictures -> the normalised VAE input at ``size`` = (H, W): antialiased bilinear resize, ToTensor,
+    Normalize([0.5], [0.5]) in one kernel (gmd_prepare_sdr).  layout "nchw": [B,3,H,W]; "nhwc": [B,H*W,cp] channels-last with the
+    padding channels zeroed (what ``AutoencoderKL.encode_nhwc`` consumes)."""
+    _dev(images_u8)
+    if images_u8.dtype != torch.uint8 or images_u8.dim() != 4 or images_u8.shape[-1] != 3:
+        raise HipExtensionError(f"prepare_sdr expects uint8 [B, h, w, 3], got {images_u8.dtype} {tuple(images_u8.shape)}")
+    if layout not in ("nchw", "nhwc"):
+        raise HipExtensionError("prepare_sdr: layout must be 'nchw' or 'nhwc'")
+    B, h, w = (int(v) for v in images_u8.shape[:3])
+    H, W = int(size[0]), int(size[1])
+    out = torch.empty((B, 3, H, W) if layout == "nchw" else (B, H * W, cp), dtype=dtype, device=images_u8.device)
+    tm, t0 = _timed("prepare_sdr")
+    check(lib().gmd_prepare_sdr(_ptr(images_u8), B, h, w, _ptr(out), dtype_code(dtype), 0 if layout == "nchw" else 1, int(cp), H, W, _stream()),
+          "gmd_prepare_sdr")
+    if tm:  # the picture read once + the output written once
+        tm.end("prepare_sdr", 0.0, images_u8.numel() + out.numel() * out.element_size(), t0)
     return out
 
 

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GMD_ABI_VERSION 12
+#define GMD_ABI_VERSION 13
 #define GMD_WS_TAIL_BYTES 65536 /* see "WORKSPACE CONTRACT" at gmd_gemm_nt */
 
 #define GMD_OK 0
@@ -88,6 +88,43 @@ int gmd_hdr_tail(const void* sdr_dec, const void* gm_dec, int in_dtype, int in_l
                  int B, int H, int W, float qmax, float eps, int flags,
                  float* sdr_img, float* gm_img, uint8_t* sdr_u8, uint8_t* gm_u8,
                  float* hdr, float* hdr_file, uint16_t* hdr_u16, gmd_stream_t stream);
+
+/* The fused tail at an OUTPUT SIZE OF ITS OWN (H, W): both operands are resampled onto it inside the kernel, so a full-size HDR is
+ * written without a full-size float intermediate.  Replaces the closing lines of every Stage-3 driver of the reference:
+ *   cv2.resize(sdr_image_decoded / gm_image, size, INTER_LINEAR) then apply_gm_to_sdr
+ *                                  scripts/stage2/experiments/demo_training_loop.py:291-304, scheduler_tuning.py:234-320,
+ *                                  accelerate_training_smoke.py:208-275, batch_size_sweep.py:266-267
+ *   the gain map applied to the source picture's own pixels (original_hdr_image)    scripts/inference/generate_hdr.py:262-265
+ * sdr: [B,.,hs,ws], gm_dec: [B,.,hg,wg], decoder outputs in [-1,1] in the layouts / dtypes of the entry point above (in_layout 2 =
+ * [B,h*w,4], 4th channel ignored).  Per operand and output pixel: clamp(x/2+0.5, 0, 1) of each of the four taps (the scripts resize the
+ * post-processed image), then the bilinear combination with half-pixel centres and edge clamp (cv2.INTER_LINEAR on float32 =
+ * F.interpolate(mode="bilinear", align_corners=False)).  Per axis, output index i, n_in -> n_out, all in int32:
+ *   num = max((2i+1) n_in - n_out, 0), den = 2 n_out, i0 = num / den, lambda = float(num - i0 den) / float(den), i1 = min(i0+1, n_in-1)
+ *   value = (1-ly) ((1-lx) p00 + lx p01) + ly ((1-lx) p10 + lx p11)
+ * An operand whose size equals (H, W) has lambda = 0 everywhere: the value is the tap itself, bit for bit.
+ * flags bit 0: clamp hdr to [0, qmax+1]; bit 1: `sdr` is instead a uint8 [B,H,W,3] picture already at the output size (hs = H and
+ * ws = W required), read as float(u8) / 255.0f (ToTensor).
+ * Outputs: the seven of the entry point above at [B,H,W,3] plus hdr_rgbe, uint8 [B,H,W,4]: Ward's RGBE encoding of hdr_file (the
+ * arithmetic of the RGBE entry point below), so a writer never reads a full-size float image back.  Any output pointer may be NULL;
+ * float outputs 4-byte, hdr_u16 2-byte, hdr_rgbe 4-byte aligned.  SIZE LIMIT: B >= 1 and every one of hs, ws, hg, wg, H, W in
+ * 1..16384, which keeps each integer numerator above below 2^30; anything else is GMD_ERR_INVALID before a launch. */
+int gmd_hdr_tail_resized(const void* sdr, int hs, int ws, const void* gm_dec, int hg, int wg, int in_dtype, int in_layout,
+                         int B, int H, int W, float qmax, float eps, int flags,
+                         float* sdr_img, float* gm_img, uint8_t* sdr_u8, uint8_t* gm_u8,
+                         float* hdr, float* hdr_file, uint16_t* hdr_u16, uint8_t* hdr_rgbe, gmd_stream_t stream);
+
+/* The way in: uint8 [B,h,w,3] picture -> Resize((H, W), BILINEAR) -> ToTensor -> Normalize([0.5], [0.5]), the VAE encoder's input
+ * (scripts/stage2/experiments/demo_training_loop.py:205-211, 230; scheduler_tuning.py, accelerate_training_smoke.py and
+ * batch_size_sweep.py build the same transform).  The resize is the antialiased triangle filter of PIL's Image.resize(BILINEAR) /
+ * F.interpolate(mode="bilinear", antialias=True), here without PIL's byte rounding between its two passes.  Per axis, n_in >= n_out:
+ * tap j of output i has the integer weight numerator max(0, 2 n_in - |(2j+1) n_out - (2i+1) n_in|); n_in < n_out: the two bilinear
+ * taps of the entry point above (numerators den - r and r).  Weights are normalised by their integer sum over the in-range taps; the
+ * 2-D weight is the product.  Then v = resized / 255, out = (v - 0.5) / 0.5, one rounding to out_dtype (F32 / BF16 / F16).  Equal
+ * sizes give ToTensor + Normalize exactly.  out_layout 0: [B,3,H,W]; 1: [B,H*W,cp] channels-last with channels 3..cp-1 zeroed (the
+ * padded input of the encoder's first convolution; 3 <= cp <= 64).  SIZE LIMIT: B >= 1 and h, w, H, W in 1..16384 (numerators below
+ * 2^30); anything else is GMD_ERR_INVALID before a launch. */
+int gmd_prepare_sdr(const uint8_t* src, int B, int h, int w, void* out, int out_dtype, int out_layout, int cp, int H, int W,
+                    gmd_stream_t stream);
 
 /* tone_mapping.py:60-71 apply_gm_to_sdr (clamp!=0) / formal_improved.py:34-45 (clamp==0); any shape, n elements */
 int gmd_apply_gm_to_sdr(const float* gm, const float* sdr, float* out, int64_t n,
