@@ -22,7 +22,7 @@
 // gemm_split.hip: float32 on the matrix cores as three float16 products (GMD_F32S / GMD_F32SW)
 int gmd_launch_split_gemm(const void* params, int presplit, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
 int gmd_launch_split_conv(const void* params, int presplit, int B, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
-int gmd_split_plan_ksplit(int M, int N, int K, int64_t ws_bytes);
+int gmd_split_plan_ksplit_usable(int M, int N, int K, int64_t ws_bytes);
 int gmd_split_colstats_ok(int M, int N, int K, int batch, int64_t ws_bytes, int bucket);
 int gmd_split_out_ok(int M, int N, int K, int geglu, int64_t ws_bytes);
 int gmd_split_qkv_vt_ok(int M, int N, int K, int vt_col0, int vt_tokens, int64_t ws_bytes);
@@ -2818,6 +2818,12 @@ int gmd_gemm_plan_info(int dtype, int M, int N, int K, int batch, int64_t worksp
     return GMD_OK;
 }
 
+// K slices of a float32 matrix-core (GMD_F32S / GMD_F32SW / GMD_F32SA) gmd_gemm_nt launch: slabs + splitk_reduce_f32_kernel when > 1
+int gmd_split_plan_ksplit(int M, int N, int K, int64_t workspace_bytes) {
+    if (M <= 0 || N <= 0 || K <= 0 || K % 32) return 0;
+    return gmd_split_plan_ksplit_usable(M, N, K, gmd_ws_usable_bytes(workspace_bytes));
+}
+
 // 1 when a float32-split gmd_gemm_nt launch of these dimensions can take out_dtype = GMD_F32SA (store its result pre-split)
 int gmd_gemm_out_split_ok(int M, int N, int K, int geglu, int64_t workspace_bytes) { return gmd_split_out_ok(M, N, K, geglu, gmd_ws_usable_bytes(workspace_bytes)); }
 
@@ -2962,7 +2968,7 @@ bool conv_out_shape(int Hin, int Win, int stride, int& upsample, int pad_mode, i
 
 // split-K factor the conv launch will use (1 = unsplit); the same planners the launch itself calls
 int conv_plan_ksplit(int dtype, int64_t M, int Cin, int Cout, int64_t ws_bytes) {
-    if (gmd_is_split(dtype)) return gmd_split_plan_ksplit((int)M, Cout, 9 * Cin, ws_bytes);
+    if (gmd_is_split(dtype)) return gmd_split_plan_ksplit_usable((int)M, Cout, 9 * Cin, ws_bytes);
     if (gmd_is_half(dtype)) return make_plan((int)M, Cout, 9 * Cin, 1, ws_bytes, false).ksplit;
     return 1;
 }

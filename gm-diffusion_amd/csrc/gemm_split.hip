@@ -1074,7 +1074,8 @@ int gmd_split_qkv_vt_ok(int M, int N, int K, int vt_col0, int vt_tokens, int64_t
 }
 
 // split-K factor launch_split_any will choose (no GEGLU): gmd_conv3x3_groupnorm / gmd_conv3x3_gn_fusable of gemm.hip
-int gmd_split_plan_ksplit(int M, int N, int K, int64_t ws_bytes) { return make_split_plan(M, N, K, 1, ws_bytes).ksplit; }
+// (ws_bytes: the USABLE bytes; the C ABI's gmd_split_plan_ksplit of gemm.hip takes the whole workspace)
+int gmd_split_plan_ksplit_usable(int M, int N, int K, int64_t ws_bytes) { return make_split_plan(M, N, K, 1, ws_bytes).ksplit; }
 
 void gmd_split_set_lc(int mode) { g_split_lc_mode = mode; }
 

@@ -266,7 +266,21 @@ int gmd_splitk_fixup_max(int max_slices);
  * allocating it) and every launch leaves them zero; only workspace_bytes - GMD_WS_TAIL_BYTES are used for partial sums, and the plan
  * queries (gmd_gemm_colstats_plan, gmd_gemm_plan_info, gmd_gemm_qkv_vt_ok, gmd_gemm_out_split_ok, gmd_conv3x3_gn_fusable) take the
  * same workspace_bytes the launch will get.  One workspace serves ONE stream (or one captured graph) at a time: launches that may
- * run concurrently need workspaces of their own. */
+ * run concurrently need workspaces of their own.
+ * SCRATCH EXTENTS.  With usable = workspace_bytes - GMD_WS_TAIL_BYTES, a launch of ks > 1 K slices writes, from the start of the buffer,
+ *   slab extent     = ks * M * N * 4 bytes (one float32 [M, N] slab per slice, summed by a reduction launch or by the GroupNorm of
+ *                     gmd_conv3x3_groupnorm), or
+ *   fragment extent = (ks - 1) * tiles * bm * bn * 4 bytes, tiles = ceil(M / bm) * ceil(N / bn) (the in-kernel reduction of
+ *                     gmd_splitk_fixup_max: whole accumulator tiles of the slices 0 .. ks-2, ragged tiles included),
+ * and nothing else: no byte at or beyond `usable` other than the counters, which end at zero, and no byte at or beyond workspace_bytes.
+ * K is split into ks slices only if the slab extent of ks fits `usable`: where it does not, the planner takes fewer slices or none (a
+ * slice count forced with gmd_gemm_plan_override: none, ks = 1); the in-kernel reduction is taken only if, in addition, the fragment
+ * extent fits `usable` and tiles <= GMD_WS_TAIL_BYTES / 4 (otherwise: slabs).  Both give the same bits.
+ * DISPATCH-ORDER ASSUMPTION of the in-kernel reduction: the last slice of a tile waits (bounded) for the other slices' workgroups, so
+ * those must already hold a CU: the library relies on the hardware dispatching workgroups in increasing linear id (x fastest, the K
+ * slice z slowest), round-robin over the XCDs.  There is no release / acquire pair between the slices; the hand-off rests on the
+ * cache-coherence bits of the fragment stores and loads and an agent-scope counter.  GMD_SPLITK_FIXUP=0 in the environment (or
+ * gmd_splitk_fixup_max(0)) is the escape hatch: every split launch then takes the slab path. */
 int gmd_gemm_nt(const void* A, const void* W, void* C, int dtype, int out_dtype,
                 int M, int N, int K, int64_t lda, int64_t ldw, int64_t ldc,
                 int batch, int64_t strideA, int64_t strideW, int64_t strideC,
@@ -312,6 +326,11 @@ int gmd_gemm_qkv_vt(const void* A, const void* W, void* C, void* Vt, int dtype, 
 /* 1 when a float32-split gmd_gemm_nt launch of these dimensions (batch 1) can take out_dtype = GMD_F32SA, i.e. store its [M, N] (GEGLU:
  * [M, N/2]) result pre-split for the contraction that follows: an unsplit launch of full 128-row tiles through the row epilogues. */
 int gmd_gemm_out_split_ok(int M, int N, int K, int geglu, int64_t workspace_bytes);
+
+/* K slices a float32 matrix-core gmd_gemm_nt launch (GMD_F32S / GMD_F32SW / GMD_F32SA, batch 1, no GEGLU) of these dimensions takes with
+ * this workspace: > 1 = float32 slabs (the slab extent of the WORKSPACE CONTRACT) summed by a reduction launch.  0 for a shape the
+ * path does not take (K % 32 != 0).  Pure host function: tests use it to know what they exercise. */
+int gmd_split_plan_ksplit(int M, int N, int K, int64_t workspace_bytes);
 
 /* Debug facility like gmd_gemm_plan_override (refused unless the process has GMD_TUNING=1): how stride-1 gmd_conv3x3 launches on
  * 256-row ping-pong tiles fetch their activations -- 2 (the default) = the tile's input patch resident in LDS, continuous consumers;
