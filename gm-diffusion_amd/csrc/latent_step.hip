@@ -117,6 +117,46 @@ __global__ __launch_bounds__(kThreads) void ddpm_step_kernel(
     }
 }
 
+// DDIM step (the scheduler the pipelines' docstrings name first; `eta` is its dial towards DDPM) fused with the CFG combine
+// and the pipeline's x0, in the operation order of the torch expressions of diffusers' DDIMScheduler.step (epsilon
+// prediction, float32, no FMA):
+//   p0   = (x - sqrt(1-a_t) * eps) / sqrt(a_t)                      pred_original_sample [clamped to +-clip_range]
+//   pe   = use_clipped ? (x - sqrt(a_t) * p0) / sqrt(1-a_t) : eps   pred_epsilon
+//   prev = sqrt(a_prev) * p0 + dir_coeff * pe                       dir_coeff = (1 - a_prev - std^2) ** 0.5
+//   prev = prev + std * noise                                       eta > 0 only (noise == nullptr otherwise)
+// The add happens whenever a noise tensor is given, also with std == 0 (the last step of a set_alpha_to_one schedule): torch
+// adds the zero product there too, and -0.0 + 0.0 is not -0.0.  The noise is drawn by the HOST scheduler, as for DDPM.
+__global__ __launch_bounds__(kThreads) void ddim_step_kernel(
+    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
+    float gs, const float* __restrict__ ratio, float gr, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range,
+    int use_clipped, float sqrt_a_prev, float dir_coeff, float std, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
+    float* __restrict__ x0, float* __restrict__ pred_x0) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const int64_t n = (int64_t)B * chw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float eps;
+        if (do_cfg) {
+            const float u = eps_in[i], t = eps_in[n + i];
+            eps = u + gs * (t - u);  // dual.py:1065
+            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
+                const float resc = eps * ratio[i / chw];
+                eps = gr * resc + (1.0f - gr) * eps;
+            }
+        } else {
+            eps = eps_in[i];
+        }
+        const float xt = x[i];
+        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (never clipped)
+        float p0 = (xt - sched_sqrt_1ma * eps) / sched_sqrt_a;
+        if (clip) p0 = fminf(fmaxf(p0, -clip_range), clip_range);
+        if (pred_x0) pred_x0[i] = p0;
+        const float pe = use_clipped ? (xt - sched_sqrt_a * p0) / sched_sqrt_1ma : eps;
+        float r = sqrt_a_prev * p0 + dir_coeff * pe;
+        if (noise) r = r + std * noise[i];
+        x_prev[i] = r;
+    }
+}
+
 // one block per sample: unbiased std over chw of text eps and of the guided eps
 __global__ __launch_bounds__(kThreads) void cfg_std_ratio_kernel(const float* __restrict__ eps_in, int B, int64_t chw,
                                                                  float gs, float* __restrict__ ratio) {
@@ -250,6 +290,28 @@ int gmd_ddpm_step(const float* eps_in, const float* x, const float* noise, int B
         eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
         sched_sqrt_one_minus_alpha, clip_sample, clip_range, x0_coeff, xt_coeff, noise_scale, sqrt_alpha, sqrt_one_minus_alpha, x_prev, x0);
     GMD_CHECK_LAUNCH("gmd_ddpm_step");
+    return GMD_OK;
+}
+
+int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
+                  const float* rescale_ratio, float guidance_rescale, float sched_sqrt_alpha, float sched_sqrt_one_minus_alpha,
+                  int clip_sample, float clip_range, int use_clipped, float sqrt_alpha_prev, float dir_coeff, float std_dev,
+                  float sqrt_alpha, float sqrt_one_minus_alpha, float* x_prev, float* x0, float* pred_x0, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && chw > 0, "gmd_ddim_step: bad shape B=%d chw=%lld", B, (long long)chw);
+    if (B == 0) return GMD_OK;
+    GMD_REQUIRE(eps_in && x && x_prev, "gmd_ddim_step: null pointer");
+    GMD_REQUIRE(sched_sqrt_alpha != 0.0f && (!use_clipped || sched_sqrt_one_minus_alpha != 0.0f) &&
+                    (x0 == nullptr || sqrt_alpha != 0.0f),
+                "gmd_ddim_step: zero denominator");
+    GMD_REQUIRE(!clip_sample || clip_range > 0.0f, "gmd_ddim_step: clip_range must be positive");
+    // written as !(v >= 0) so that a NaN (the square root of a negative 1 - a_prev - std^2) is refused too
+    GMD_REQUIRE(dir_coeff >= 0.0f, "gmd_ddim_step: dir_coeff must be >= 0 (got %g)", (double)dir_coeff);
+    GMD_REQUIRE(std_dev >= 0.0f, "gmd_ddim_step: std_dev must be >= 0 (got %g)", (double)std_dev);
+    ddim_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
+        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
+        sched_sqrt_one_minus_alpha, clip_sample, clip_range, use_clipped, sqrt_alpha_prev, dir_coeff, std_dev, sqrt_alpha,
+        sqrt_one_minus_alpha, x_prev, x0, pred_x0);
+    GMD_CHECK_LAUNCH("gmd_ddim_step");
     return GMD_OK;
 }
 

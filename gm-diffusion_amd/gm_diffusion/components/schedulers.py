@@ -1,7 +1,8 @@
 """
 Schedulers for the MI355X build: ``PNDMScheduler`` (PLMS, the "50 PNDM steps" configuration of
-scripts/stage2/train_gm_unet.py:171-176) and ``DDPMScheduler``
-(scripts/inference/generate_hdr.py:162).  In the reference both come from ``diffusers``; these
+scripts/stage2/train_gm_unet.py:171-176), ``DDPMScheduler`` (scripts/inference/generate_hdr.py:162),
+``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188) and
+``DPMSolverMultistepScheduler``.  In the reference they come from ``diffusers``; these
 classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241, 610-625, 715,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
 access), ``set_timesteps``, ``timesteps``, ``order``, ``init_noise_sigma``,
@@ -29,6 +30,12 @@ from .image_processor import _Output, randn_tensor
 @dataclass
 class SchedulerOutput(_Output):
     prev_sample: torch.Tensor
+
+
+@dataclass
+class DDIMSchedulerOutput(_Output):
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
 
 
 def _betas(beta_schedule, beta_start, beta_end, n, trained_betas=None):
@@ -336,6 +343,139 @@ class DDPMScheduler(_SchedulerBase):
             v = self._get_variance(t).to(dev)
             prev = prev + (v * noise if self.config.variance_type == "fixed_small_log" else (v ** 0.5) * noise)
         return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+
+class DDIMScheduler(_SchedulerBase):
+    """DDIM: the deterministic single-history sampler the pipelines' docstrings name first (stable_diffusion_gm.py:188,
+    stable_diffusion_dual_unet.py:188; scripts/stage2/train_gm_unet.py:48, scripts/stage2/experiments/scheduler_tuning.py:178-188)
+    and the one scheduler that uses their ``eta`` argument (:612, :843): ``eta`` = 0 is DDIM, 1 is DDPM's variance.  Implements
+    diffusers' epsilon-prediction path with ``clip_sample`` and ``use_clipped_model_output``; v-prediction, thresholding and
+    zero-SNR betas raise NotImplementedError.  It keeps no history.  ``step`` / ``fused_step`` run as ONE HIP kernel
+    (gmd_ddim_step) for float32 device tensors, as the same torch expressions (``_host_step``) otherwise."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     clip_sample=True, set_alpha_to_one=True, steps_offset=0, prediction_type="epsilon", thresholding=False,
+                     dynamic_thresholding_ratio=0.995, clip_sample_range=1.0, sample_max_value=1.0,
+                     timestep_spacing="leading", rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        cfg = dict(self._defaults)
+        bad = [k for k in kwargs if k not in cfg]
+        if bad:
+            raise TypeError(f"DDIMScheduler: unexpected arguments {bad}")
+        cfg.update(kwargs)
+        self.register_to_config(**cfg)
+        if cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("only epsilon prediction without thresholding / zero-SNR rescale is implemented")
+        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.arange(0, cfg["num_train_timesteps"])[::-1].copy().astype(np.int64))
+
+    def set_timesteps(self, num_inference_steps, device=None):
+        c = self.config
+        if num_inference_steps > c.num_train_timesteps:
+            raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.config.train_timesteps`:"
+                             f" {c.num_train_timesteps} as the unet model trained with this scheduler can only handle"
+                             f" maximal {c.num_train_timesteps} timesteps.")
+        self.num_inference_steps = num_inference_steps
+        if c.timestep_spacing == "linspace":
+            timesteps = np.linspace(0, c.num_train_timesteps - 1, num_inference_steps).round()[::-1].copy().astype(np.int64)
+        elif c.timestep_spacing == "leading":
+            ratio = c.num_train_timesteps // num_inference_steps
+            timesteps = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.int64)
+            timesteps += c.steps_offset
+        elif c.timestep_spacing == "trailing":
+            ratio = c.num_train_timesteps / num_inference_steps
+            timesteps = np.round(np.arange(c.num_train_timesteps, 0, -ratio)).astype(np.int64)
+            timesteps -= 1
+        else:
+            raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'leading' or 'trailing'.")
+        self.timesteps = torch.from_numpy(timesteps).to(device)
+
+    def draws_noise(self, timestep, eta=0.0):
+        """True when ``step`` at this timestep consumes the generator: iff eta > 0, at EVERY step (the last one included, where
+        the standard deviation may be 0) -- n steps take n draws, where DDPM takes n - 1 when it reaches t == 0."""
+        return eta > 0
+
+    def _coefs(self, timestep, eta):
+        """The step's coefficients as float32 0-d tensors, evaluated exactly as diffusers' ``DDIMScheduler.step`` evaluates them:
+        (a_t ** 0.5, (1 - a_t) ** 0.5, a_prev ** 0.5, (1 - a_prev - std^2) ** 0.5, std = eta * variance ** 0.5, a_t)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        t = int(timestep)
+        prev_t = t - self.config.num_train_timesteps // self.num_inference_steps
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        b_t, b_prev = 1 - a_t, 1 - a_prev
+        variance = (b_prev / b_t) * (1 - a_t / a_prev)  # _get_variance
+        std = eta * variance ** 0.5
+        dir_coeff = (1 - a_prev - std ** 2) ** 0.5
+        return a_t ** 0.5, b_t ** 0.5, a_prev ** 0.5, dir_coeff, std, a_t
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise=None,
+                     eta=0.0, use_clipped_model_output=False, want_pred_x0=False):
+        """One HIP kernel pass (gmd_ddim_step): CFG combine (+rescale), pipeline x0, clipped x0 prediction, the DDIM update and
+        the variance noise.  The noise is drawn HERE with ``randn_tensor`` exactly where ``step`` draws it (iff eta > 0), so a
+        generator shared by the two schedulers of the dual pipeline is consumed in the reference's order.
+        Returns (prev_sample, x0 | None, pred_original_sample | None)."""
+        sa, s1, sp, dc, sd, a_t = self._coefs(timestep, eta)
+        if eta > 0:
+            if noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order: see fused_step)
+                noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        else:
+            noise = None
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        return ops.ddim_step(eps_in.contiguous(), sample.contiguous(),
+                             (sa.item(), s1.item(), sp.item(), dc.item(), sd.item(), a_t.sqrt().item(), (1 - a_t).sqrt().item()),
+                             do_cfg, guidance_scale, noise=noise, ratio=ratio, guidance_rescale=guidance_rescale,
+                             clip_range=self.config.clip_sample_range if self.config.clip_sample else None,
+                             use_clipped=use_clipped_model_output, want_x0=want_x0, want_pred_x0=want_pred_x0)
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None,
+                   eta=0.0, use_clipped_model_output=False):
+        """Same contract as ``DDPMScheduler.fused_step`` plus ``eta`` / ``use_clipped_model_output`` (device float32 tensors
+        only).  ``noise``: this step's variance noise already drawn from ``generator`` by the caller; used iff eta > 0.
+        Returns (prev_sample, x0 | None)."""
+        prev, x0, _ = self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise,
+                                        eta, use_clipped_model_output)
+        return prev, x0
+
+    def step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None,
+             return_dict=True, noise=None):
+        """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor: what ``generator`` would have
+        given at this step, so it may come together with the generator."""
+        if generator is not None and variance_noise is not None:
+            raise ValueError("Cannot pass both generator and variance_noise. Please make sure that either `generator` or"
+                             " `variance_noise` stays `None`.")
+        if variance_noise is None:
+            variance_noise = noise
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, _, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, variance_noise, eta,
+                                            use_clipped_model_output, want_pred_x0=True)
+            return (prev, p0) if not return_dict else DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+        return self._host_step(model_output, timestep, sample, eta, use_clipped_model_output, generator, variance_noise, return_dict)
+
+    def _host_step(self, model_output, timestep, sample, eta=0.0, use_clipped_model_output=False, generator=None, variance_noise=None,
+                   return_dict=True):
+        """The torch expressions of diffusers' ``DDIMScheduler.step`` (host tensors; also the reference for the kernel test)."""
+        dev = model_output.device
+        sa, s1, sp, dc, sd, _ = (c.to(dev) for c in self._coefs(timestep, eta))
+        p0 = (sample - s1 * model_output) / sa
+        pred_epsilon = model_output
+        if self.config.clip_sample:
+            p0 = p0.clamp(-self.config.clip_sample_range, self.config.clip_sample_range)
+        if use_clipped_model_output:
+            pred_epsilon = (sample - sa * p0) / s1
+        prev = sp * p0 + dc * pred_epsilon
+        if eta > 0:
+            if variance_noise is None:
+                variance_noise = randn_tensor(model_output.shape, generator=generator, device=dev, dtype=model_output.dtype)
+            prev = prev + sd * variance_noise
+        return (prev, p0) if not return_dict else DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
 
 
 class DPMSolverMultistepScheduler(_SchedulerBase):

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "ddpm_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "ddpm_step", "ddim_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -1043,6 +1043,29 @@ def ddpm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, 
                               float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), c0, ct, ns, pa, p1,
                               _ptr(x_prev), _ptr(x0), _stream()), "gmd_ddpm_step")
     return x_prev, x0
+
+
+def ddim_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, clip_range=None,
+              use_clipped=False, want_x0=False, want_pred_x0=False):
+    """Fused CFG + x0 + DDIM update.  coefs = (sched_sqrt_alpha, sched_sqrt_one_minus_alpha, sqrt_alpha_prev, dir_coeff, std_dev,
+    sqrt_alpha, sqrt_one_minus_alpha); ``noise`` is None when eta == 0 and is added whenever given (also with std_dev == 0);
+    ``clip_range`` None = no clip_sample; ``use_clipped`` = use_clipped_model_output.  Returns (x_prev, x0|None, pred_x0|None):
+    x0 is the pipeline's never-clipped prediction, pred_x0 diffusers' (clipped) pred_original_sample."""
+    _dev(eps_in, x, noise, ratio)
+    for t in (eps_in, x, noise):
+        _f32(t, "latent tensors")
+    if noise is not None and noise.shape != x.shape:
+        raise HipExtensionError("ddim_step: noise must have the sample's shape")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    x_prev = torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
+    sa, s1, sp, dc, sd, pa, p1 = (float(v) for v in coefs)
+    check(lib().gmd_ddim_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
+                              float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), int(bool(use_clipped)),
+                              sp, dc, sd, pa, p1, _ptr(x_prev), _ptr(x0), _ptr(pred_x0), _stream()), "gmd_ddim_step")
+    return x_prev, x0, pred_x0
 
 
 # ----------------------------------------------------------------------------------------------

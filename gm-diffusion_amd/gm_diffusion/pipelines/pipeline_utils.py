@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from ..components import AutoencoderKL, CLIPTextModel, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UNet2DConditionModel
+from ..components import AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UNet2DConditionModel
 from ..components.configuration import FrozenDict
 
 _LOADABLE = {
@@ -23,6 +23,7 @@ _LOADABLE = {
     "CLIPTextModel": CLIPTextModel,  # model_index.json lists it under "transformers": the HIP implementation takes over
     "PNDMScheduler": PNDMScheduler,
     "DDPMScheduler": DDPMScheduler,
+    "DDIMScheduler": DDIMScheduler,
     "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
 }
 

@@ -191,7 +191,8 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             if self._graphs_ok():
                 g_sdr = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run)
                 g_gm = self.gm_unet.graphed_forward(latents.shape[0], h, w, gm_ctx, co_run=co_run)
-            pre = self._predraw_step_noise([self.scheduler, self.gm_scheduler], ts_host, latents.shape, generator, latents.device)
+            pre = self._predraw_step_noise([self.scheduler, self.gm_scheduler], ts_host, latents.shape, generator, latents.device,
+                                           eta=extra_step_kwargs.get("eta", 0.0))
             gm_stream.wait_stream(sdr_stream)
             if gm_stream is not sdr_stream:
                 # allocated on the caller's stream, consumed (and released) by step 0 on the GM stream: without this the

@@ -342,15 +342,15 @@ class _GMPipelineBase(DiffusionPipeline):
     def _use_fused(self, latents, unet, scheduler):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
-        from ..components.schedulers import DDPMScheduler, DPMSolverMultistepScheduler
+        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 
-        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler))
+        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler))
                 and isinstance(unet, UNet2DConditionModel))
 
     PREDRAW_NOISE_BYTES = 512 << 20  # ceiling of the pre-drawn scheduler noise (host pinned copy + device copy)
 
     @staticmethod
-    def _predraw_step_noise(schedulers, ts_host, shape, generator, device):
+    def _predraw_step_noise(schedulers, ts_host, shape, generator, device, eta=0.0):
         """Stochastic schedulers on the fused path with a CPU generator: draw the variance noise of EVERY step now, in exactly
         the order the loop would consume the generator (per iteration: the schedulers in the order given -- SDR before GM,
         stable_diffusion_dual_unet.py:1077, 1093), and move it to the device in one asynchronous copy.  A draw inside the
@@ -359,16 +359,18 @@ class _GMPipelineBase(DiffusionPipeline):
         or None when there is nothing to pre-draw (deterministic scheduler, device generator, global RNG) or when the noise
         of all steps would exceed PREDRAW_NOISE_BYTES (DDPM's default 1000 steps at 1024x1024, batch 8, two schedulers is
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
+        DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
-        from ..components.schedulers import DDPMScheduler
+        from ..components.schedulers import DDIMScheduler, DDPMScheduler
 
-        if generator is None or not all(isinstance(s_, DDPMScheduler) for s_ in schedulers):
+        if generator is None or not all(isinstance(s_, (DDPMScheduler, DDIMScheduler)) for s_ in schedulers):
             return None
         gens = generator if isinstance(generator, list) else [generator]
         if any(g_.device.type != "cpu" for g_ in gens):
             return None
-        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers) if s_.draws_noise(t)]
+        draws = lambda s_, t: s_.draws_noise(t, eta) if isinstance(s_, DDIMScheduler) else s_.draws_noise(t)
+        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers) if draws(s_, t)]
         if not slots:
             return None
         nbytes = 4 * len(slots)
@@ -387,8 +389,9 @@ class _GMPipelineBase(DiffusionPipeline):
     @staticmethod
     def _fused_step_kwargs(extra_step_kwargs):
         """What ``scheduler.fused_step`` takes of the reference's ``extra_step_kwargs``: the generator (stochastic
-        schedulers draw their noise from it in call order, stable_diffusion_dual_unet.py:1077, 1093)."""
-        return {"generator": extra_step_kwargs["generator"]} if "generator" in extra_step_kwargs else {}
+        schedulers draw their noise from it in call order, stable_diffusion_dual_unet.py:1077, 1093) and ``eta``, which
+        ``prepare_extra_step_kwargs`` includes only for a scheduler whose ``step`` takes it (DDIM)."""
+        return {k: extra_step_kwargs[k] for k in ("generator", "eta") if k in extra_step_kwargs}
 
     def _default_hw(self, height, width):
         if not height or not width:
@@ -491,7 +494,8 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
             hw = latents.shape[-2:]
             shared = self._cfg_shared(self.unet, do_cfg)
             nb = (2 if do_cfg else 1) * latents.shape[0]
-            pre = self._predraw_step_noise([self.scheduler], ts_host, latents.shape, generator, latents.device)
+            pre = self._predraw_step_noise([self.scheduler], ts_host, latents.shape, generator, latents.device,
+                                           eta=extra_step_kwargs.get("eta", 0.0))
             graph = self.unet.graphed_forward(nb, hw[0], hw[1], ctx, cfg_shared=shared) if self._graphs_ok() else None
 
         with self.progress_bar(total=num_inference_steps) as progress_bar:

@@ -30,7 +30,7 @@
 extern "C" {
 #endif
 
-#define GMD_ABI_VERSION 13
+#define GMD_ABI_VERSION 14
 #define GMD_WS_TAIL_BYTES 65536 /* see "WORKSPACE CONTRACT" at gmd_gemm_nt */
 
 #define GMD_OK 0
@@ -204,6 +204,24 @@ int gmd_ddpm_step(const float* eps_in, const float* x, const float* noise, int B
                   float sched_sqrt_alpha, float sched_sqrt_one_minus_alpha, int clip_sample, float clip_range,
                   float x0_coeff, float xt_coeff, float noise_scale, float sqrt_alpha, float sqrt_one_minus_alpha,
                   float* x_prev, float* x0, gmd_stream_t stream);
+
+/* DDIM step -- the scheduler the pipelines' docstrings name first (stable_diffusion_gm.py:188, stable_diffusion_dual_unet.py:188)
+ * and the only one that uses their `eta` argument (:612, :843) -- fused with the same CFG combine / rescale and pipeline x0 as
+ * gmd_latent_step, in the float32 operation order of diffusers' DDIMScheduler.step (epsilon prediction):
+ *   p0 = (x - sched_sqrt_one_minus_alpha*eps)/sched_sqrt_alpha [clamp +-clip_range]          pred_original_sample
+ *   pe = use_clipped ? (x - sched_sqrt_alpha*p0)/sched_sqrt_one_minus_alpha : eps             pred_epsilon
+ *   x_prev = sqrt_alpha_prev*p0 + dir_coeff*pe [ + std_dev*noise when noise != NULL (eta > 0) ]
+ * sqrt_alpha_prev = a_prev ** 0.5, std_dev = eta * variance ** 0.5, dir_coeff = (1 - a_prev - std_dev^2) ** 0.5: float32
+ * scalars computed by the host exactly as diffusers computes its 0-dim tensors.  The noise is added whenever it is given,
+ * also with std_dev == 0 (diffusers adds it iff eta > 0, at every step); it is drawn by the host scheduler from the caller's
+ * generator, in the reference's order (SDR first, GM second).  x0 (the pipeline's, never clipped) and pred_x0 (the clipped p0,
+ * diffusers' pred_original_sample) may be NULL.  dir_coeff and std_dev must be >= 0 (a NaN is refused). */
+int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw,
+                  int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                  float sched_sqrt_alpha, float sched_sqrt_one_minus_alpha, int clip_sample, float clip_range,
+                  int use_clipped, float sqrt_alpha_prev, float dir_coeff, float std_dev,
+                  float sqrt_alpha, float sqrt_one_minus_alpha,
+                  float* x_prev, float* x0, float* pred_x0, gmd_stream_t stream);
 
 /* per-sample unbiased std of the text eps and of the guided eps -> ratio[b] = std_text/std_cfg
  * (rescale_noise_cfg, stable_diffusion_dual_unet.py:88-91) */
