@@ -434,7 +434,9 @@ int gmd_softmax_rows(const float* S, int64_t lds, void* P, int out_dtype, int64_
 
 /* GroupNorm statistics over channels-last X [B,HW,C] -> per (b,c) affine
  * scale_shift[b][c] = {rstd*gamma[c], beta[c]-mean*rstd*gamma[c]}.
- * workspace: float32, at least B*nsplit*G*2 floats where nsplit = gmd_groupnorm_nsplit(HW). */
+ * workspace: float32, at least B*nsplit*G*2 floats where nsplit = gmd_groupnorm_nsplit(HW).  Every one of these B*nsplit*G*2
+ * floats is written by each launch (workspace[b][split][g] = {sum, sumsq} of that block's rows; a block whose row range is empty
+ * stores zeros) and nothing is read before it is written, so the buffer may hold anything on entry; no float beyond them is touched. */
 int gmd_groupnorm_nsplit(int64_t HW);
 int gmd_groupnorm_stats(const void* X, int dtype, int B, int64_t HW, int C, int G, float eps,
                         const float* gamma, const float* beta, float* workspace,

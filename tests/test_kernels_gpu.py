@@ -8,6 +8,8 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from stats_handoff import assert_entries, bucket_ref_bound, bucket_sums as _bucket_sums  # (float64 {sum, sumsq} per 64 rows x bucket of columns)
+
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda"
@@ -792,13 +794,6 @@ def test_plan_override_cannot_bypass_geglu_tile_rule():
 # ---------------------------------------------------------------------------------------------
 # GroupNorm statistics out of the producer's epilogue
 # ---------------------------------------------------------------------------------------------
-def _bucket_sums(y, bucket):
-    """float64 {sum, sumsq} of the stored values per 64-row block and per bucket of adjacent columns."""
-    M, N = y.shape
-    v = y.double().cpu().view(M // 64, 64, N // bucket, bucket)
-    return torch.stack([v.sum((1, 3)), (v * v).sum((1, 3))], -1)
-
-
 @pytest.mark.parametrize("dtype", HALF)
 @pytest.mark.parametrize("kind", ["conv_res", "conv_rowbias", "conv_up", "gemm_res"])
 def test_colstats_from_producer_epilogue(dtype, kind):
@@ -836,6 +831,7 @@ def test_colstats_from_producer_epilogue(dtype, kind):
     ref = _bucket_sums(y.view(-1, C), o.COLSTATS_BUCKET)
     assert tuple(st.shape) == tuple(ref.shape)
     assert rel_err(st, ref) < 2e-6 and max_err(st[..., 0], ref[..., 0]) < 2e-3
+    assert_entries(st, *bucket_ref_bound(y.view(-1, C), o.COLSTATS_BUCKET), f"colstats {kind} {dtype}")  # ... and every entry on its own
 
 
 @pytest.mark.parametrize("B,H,ci,co", [(2, 64, 320, 320), (4, 32, 640, 640), (4, 32, 1280, 640)])
@@ -859,6 +855,7 @@ def test_split_launch_with_in_kernel_reduction_emits_statistics(B, H, ci, co):
     st, C = y._colstats
     ref = _bucket_sums(y.view(-1, C), o.COLSTATS_BUCKET)
     assert tuple(st.shape) == tuple(ref.shape) and rel_err(st, ref) < 2e-6 and max_err(st[..., 0], ref[..., 0]) < 2e-3
+    assert_entries(st, *bucket_ref_bound(y.view(-1, C), o.COLSTATS_BUCKET), f"colstats of a split launch {B}x{H}x{H}x{co}")  # ... and every entry on its own
     # ... and a GroupNorm fed from them equals the GroupNorm that computes its own
     gamma, beta = torch.randn(co, generator=g).to(DEV), torch.randn(co, generator=g).to(DEV)
     n_cs = o.groupnorm(y, B, 32, gamma, beta, 1e-5, silu=True)
