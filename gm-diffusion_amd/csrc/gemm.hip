@@ -19,15 +19,6 @@
 #include <stdlib.h>
 #include <type_traits>
 
-// gemm_split.hip: float32 on the matrix cores as three float16 products (GMD_F32S / GMD_F32SW)
-int gmd_launch_split_gemm(const void* params, int presplit, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
-int gmd_launch_split_conv(const void* params, int presplit, int B, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
-int gmd_split_plan_ksplit_usable(int M, int N, int K, int64_t ws_bytes);
-int gmd_split_colstats_ok(int M, int N, int K, int batch, int64_t ws_bytes, int bucket);
-int gmd_split_out_ok(int M, int N, int K, int geglu, int64_t ws_bytes);
-int gmd_split_qkv_vt_ok(int M, int N, int K, int vt_col0, int vt_tokens, int64_t ws_bytes);
-void gmd_split_set_lc(int mode);
-
 namespace {
 
 // Fused epilogue for 8 consecutive columns n..n+7 of row m (bf16 activations): alpha, bias, per-group row
@@ -1717,7 +1708,7 @@ __global__ __launch_bounds__(512, 2) void gemm_lc_kernel(const GemmParams p) {
 // + 4 loader waves on a tile of 256 output pixels x (32 TN) channels -- but the activation operand is not re-fetched per filter tap.
 //
 // Why: the implicit GEMM above pulls every input pixel through the CU nine times (once per tap): 32 KB of A + 20 KB of W per 64-deep
-// K step.  The two-stream pipeline is bound by what the CUs can ingest from L2 (~36 B/clk each, make_plan), so the bytes are what
+// K step.  The two-stream pipeline is bound by what the CUs can ingest from L2 (~36 B/clk each, make_plan of gemm_plan.cpp), so the bytes are what
 // counts.  Here a tile's input patch -- its rows of pixels plus a one-pixel halo, 64 channels deep: (R+2) x (W+2) pixels x 128 B,
 // at most 50 KB -- is loaded ONCE per 64-channel block into a double-buffered LDS image and all nine taps read their A fragments
 // from it at shifted rows (a tap is an LDS address offset); only the weights stream per K step (20 KB): 25.6 KB per K step instead of 52.
@@ -2284,206 +2275,6 @@ __global__ __launch_bounds__(256) void gemm_f32_kernel(const GemmParams p) {
     }
 }
 
-struct Plan {
-    int bm, bn, pf, ksplit;
-};
-
-// Channel block of the ring kernel's conv3x3 K order.  The tiles resident on one XCD (64 = 32 CUs x 2 workgroups, a
-// contiguous run of the n-fastest tile order) read the same input rows once per filter tap; walking ALL channels of a tap
-// before the next tap makes the re-read distance rows x Cin x 2 bytes, which for Cin >= 640 at 64x64 (5.2 MB) no longer
-// fits the XCD's 4 MiB L2 (rocprofv3 FETCH_SIZE: 9.1x the algorithmic reads on 8x64x64 640->320,
-// profiles/r01_pmc_conv_attention_current.txt).  Blocks of `cblk` channels bring the distance back under 3 MB
-// (rocprofv3 after: 1.97x, 125.5 -> 118.8 us; profiles/r02_pmc_conv_gemm_traffic.txt).  Shapes whose rows already fit keep
-// the tap-major order (cblk == Cin): at 2.6 MB (32x32, Cin 1280) the blocked order measured slower, not faster.
-bool tuning_enabled();
-int conv_channel_block(int B, int Hin, int Win, int Cin, int Cout, int dtype) {
-    if (dtype == GMD_F32) return Cin;
-    if (tuning_enabled()) {  // experiments only (GMD_TUNING=1): GMD_CONV_CBLK=<multiple of 64 dividing Cin>
-        const char* e = getenv("GMD_CONV_CBLK");
-        const int v = e ? atoi(e) : 0;
-        if (v >= 64 && v % 64 == 0 && Cin % v == 0) return v;
-    }
-    const int64_t rows_total = (int64_t)B * Hin * Win;
-    const int tiles_n = (Cout + 159) / 160;
-    const int64_t rows_resident = (int64_t)(64 / tiles_n > 0 ? 64 / tiles_n : 1) * 128;  // input rows under one XCD's resident tiles
-    const int64_t rows = rows_total / 8 < rows_resident ? (rows_total + 7) / 8 : rows_resident;
-    const int64_t budget = 3ll << 20;
-    if (rows * Cin * 2 <= budget) return Cin;
-    int best = 64;
-    for (int d = 64; d < Cin; d += 64)
-        if (Cin % d == 0 && rows * d * 2 <= budget) best = d;
-    return best;
-}
-
-// Kernel-tuning override (debug only: tools/, never the product path).  It takes effect only in a process that has
-// GMD_TUNING=1 in its environment -- both the GMD_GEMM_FORCE seed read when the library is loaded and the in-process
-// gmd_gemm_plan_override() -- and every forced plan still passes plan_unsupported() below, the ONE place that refuses a
-// kernel lacking the epilogue a launch asks for (round 2: five memory-access faults of tools/bench_graph_ops.py under forced
-// odd-TN ring tiles, whose plain epilogue stored [M, N] into the [M, N/2] output of the fused-GEGLU projection).
-bool tuning_enabled() {
-    const char* t = getenv("GMD_TUNING");
-    return t && t[0] == '1';
-}
-struct Force {
-    int bm = 0, bn = 0, pf = 0, ks = 0;
-    Force() {
-        if (!tuning_enabled()) return;
-        if (const char* f = getenv("GMD_GEMM_FORCE")) sscanf(f, "%d,%d,%d,%d", &bm, &bn, &pf, &ks);
-    }
-};
-Force g_force;  // read once when the library is loaded
-// GMD_PP=0 keeps the round-3 plans (A/B measurements of whole runs; read once when the library is loaded)
-const bool g_pp_enabled = [] { const char* e = getenv("GMD_PP"); return !(e && e[0] == '0'); }();
-// How stride-1 convolutions on 256-row ping-pong tiles fetch their activations: 0 (default since the end of round 5) = per-tap implicit
-// GEMM (gemm_pp_kernel<CONV>); 2 = input patch resident in LDS, continuous consumers (conv_patch_cont_kernel); 1 = patch resident,
-// ping-pong consumers (conv_patch_kernel).  GMD_CONV_PATCH seeds it when the library is loaded; gmd_conv_patch_override() changes it
-// in-process for A/B runs and tests (GMD_TUNING=1 only).  Whole-run A/Bs: round 4 (launch-by-launch plans) 838.7 / 840.6 / 837.5 ms for
-// 0 / 1 / 2 -- level, and the patch forms pull half the bytes from L2 (25.6 instead of 52 KB per K step), so 2 became the default; at
-// the end of round 5 (co-running plan family, in-kernel reduction, the shorter epilogue) the per-tap kernel is 1.0 % FASTER on the wall
-// of the two-stream pipeline (764.1 -> 756.4 ms, 4 of 4 interleaved rounds; 765.1 -> 756.8, 2 of 2), level with the streams serialised
-// (922.1 / 921.0) and at batch 8 (1266.6 / 1265.2), and level or ahead launch by launch (8x64x64 320->320 61.0 -> 58.4 us, 640->320
-// 113.7 -> 111.4): profiles/r05_ab_conv_patch_mode.txt.  The patch kernels stay in the library (tests, A/B).
-int g_conv_patch_mode = [] { const char* e = getenv("GMD_CONV_PATCH"); return (e && e[0] >= '0' && e[0] <= '2') ? e[0] - '0' : 0; }();
-// Plan family (round 5, see make_plan): 0 = the plan that is fastest launch by launch when the launch has the chip to itself (direct
-// calls, single-stream pipelines, the VAE); 1 = the co-running family -- 256-row tiles everywhere, filled up with K slices -- for
-// launches that share the chip with a second stream's kernels (the dual-UNet pipeline's two forwards).  The calling thread selects
-// it with gmd_gemm_plan_family(); GMD_PP=b / GMD_PP=1 pin family 1 / 0 for the whole process (A/B runs), read once at load time.
-const int g_family_pin = [] { const char* e = getenv("GMD_PP"); return (e && e[0] == 'b') ? 1 : ((e && e[0] == '1') ? 0 : -1); }();
-thread_local int t_plan_family = 0;
-// K slices of the co-running family: until about g_f1_target workgroups, at least g_f1_min_steps K steps each (GMD_F1_TARGET /
-// GMD_F1_MIN_STEPS: whole-run A/B only).  The target was 256 -- one workgroup per CU -- until the end of round 5; HALF the chip is
-// better: 256 -> 128: 761.5 -> 744.5 ms per batch (-2.2 %, 3 of 3 interleaved rounds), 1320.4 -> 1307.3 at batch 8 (-1.0 %); 160 / 144:
-// 747.7 / 746.3; 112: 766.8 (the 80-tile projections lose their second slice); 96 / 64 / 32: 768.9 / 780.3 / 813.8; 320: +4.4 %
-// (profiles/r05_ab_f1_slice_target.txt).  Fewer slices = fewer prologues, fragment round trips and finisher waits per product: CU-time,
-// which is what two forwards sharing the chip pay for; the other stream fills the CUs a launch leaves free.
-const int g_f1_target = [] { const char* e = getenv("GMD_F1_TARGET"); return e ? atoi(e) : 128; }();
-const int g_f1_min_steps = [] { const char* e = getenv("GMD_F1_MIN_STEPS"); return e ? atoi(e) : 8; }();
-const bool g_f1_bn128 = [] { const char* e = getenv("GMD_F1_BN128"); return !(e && e[0] == '0'); }();  // GMD_F1_BN128=0: A/B
-// In-kernel split-K reduction up to this many K slices (0 = off: slabs + reduction launch everywhere).  GMD_SPLITK_FIXUP=<n>, read once.
-int g_fixup_max = [] { const char* e = getenv("GMD_SPLITK_FIXUP"); return e ? atoi(e) : 4; }();  // gmd_splitk_fixup_max() changes it in-process
-inline bool big_tiles() { return (g_family_pin >= 0 ? g_family_pin : t_plan_family) == 1; }
-
-// Tile / split-K selection.  All SD-1.5 channel widths (320, 640, 1280, 2560, 5120, 10240) are multiples of
-// 160, the VAE widths (128, 256, 512) of 128.  Launches that would leave most of the 256 CUs idle and have a
-// deep K (the 8x8 / 16x16 UNet levels: K up to 23040) are split along K.
-Plan make_plan(int M, int N, int K, int batch, int64_t ws_bytes, bool pair_tiles, bool want_cs = false) {
-    Plan pl{64, 64, 0, 1};  // pf 0 = LDS-DMA pipeline (fastest measured); 1/2 = register-staged fallbacks
-    if (M >= 96 && N >= 96) {
-        pl.bm = 128;
-        pl.bn = (N % 160 == 0 && !pair_tiles) ? 160 : 128;  // GEGLU needs an even number of 16-column tiles per wave
-    }
-    // GMD_GEMM_FORCE="bm,bn,pf,ksplit" (0 = keep heuristic): tuning experiments only (tools/bench_gemm.py).  Parsed ONCE per
-    // process
-    // -- the launch path itself never touches the environment; gmd_gemm_plan_override() changes it in-process for A/B runs.
-    const int fbm = g_force.bm, fbn = g_force.bn, fpf = g_force.pf, fks = g_force.ks;
-    if (fbm && fbn) { pl.bm = fbm; pl.bn = fbn; }
-    if (fpf) pl.pf = fpf == 9 ? 0 : fpf;  // 9 selects the LDS-DMA pipeline (pf 0)
-    int64_t tiles = (int64_t)((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn) * batch;
-    const int nk = K / BK;
-    if (batch == 1 && tiles < 160 && nk >= 24 && !pair_tiles) {  // K >= 1536: the slab reduction (a second launch) must pay for itself
-        // whole waves of blocks: 512 (two per CU) when the tile grid is at least a quarter of the chip, else 256 (the
-        // fp32 slab traffic of more slices costs more than the second resident block buys) -- measured, tools/bench_gemm.py
-        int ks = (int)(((tiles >= 64 ? 512 : 256) + tiles / 2) / tiles);
-        if (ks > nk / 8) ks = nk / 8;  // at least 8 K steps (512 channels) per slice
-        if (ks > 16) ks = 16;
-        if (ks > 1 && (int64_t)ks * M * N * (int64_t)sizeof(float) <= ws_bytes) pl.ksplit = ks;
-    }
-    // one workgroup per CU (224..256 large tiles) leaves every SIMD with a single wave; with a very deep K (>= 10240: the
-    // 32x32 up-block convolutions over concatenated inputs) two slices -- two workgroups per CU -- pay for the slab reduction
-    // (tools/bench_graph_ops.py: 1280->640 149.9 -> 137.0 us, 1920->640 208.6 -> 181.1 us; 640->640, K = 5760, loses)
-    if (batch == 1 && pl.bm == 128 && tiles >= 224 && tiles <= 256 && nk >= 160 && !pair_tiles &&
-        2 * (int64_t)M * N * (int64_t)sizeof(float) <= ws_bytes)
-        pl.ksplit = 2;
-    // batched, operand-swapped projections (V^T[b] = W_v x_b^T: M = channels <= 640, N = tokens): 128-row tiles leave a
-    // ragged third row block at M = 320 and lose to 64x64 tiles even at M = 640 (tools/bench_vt.py: 27.9 -> 18.4 us, 17.2 -> 15.7 us)
-    if (pl.ksplit == 1 && batch > 1 && M <= 640 && pl.bm == 128 && !pair_tiles && !(fbm && fbn)) {
-        pl.bm = 64;
-        pl.bn = 64;
-    }
-    if (pl.ksplit == 1 && tiles < 256 && pl.bm == 128 && !(fbm && fbn)) {  // cannot fill the chip: 4-5x more, smaller tiles
-        pl.bm = 64;
-        pl.bn = 64;
-    }
-    if (fks) pl.ksplit = ((int64_t)fks * M * N * (int64_t)sizeof(float) <= ws_bytes && batch == 1) ? fks : 1;
-    // Round-4 kernels: one workgroup per CU with dedicated LDS-DMA loader waves (gemm_pp_kernel, code 283: 256-row tiles;
-    // gemm_lc_kernel, code 244: 128- / 64-row tiles for launches with about one tile per CU).
-    //
-    // DEFAULT POLICY -- the plan that is fastest launch by launch (tools/sweep_pp.py --round3, device time inside a HIP graph: -11 % /
-    // -15 % summed over the UNet's linear + convolution launches at batch 8 / 4 against the round-3 plans; every row of the vendor-
-    // library yardstick, tools/vs_library_gemm.py):
-    //   * ping-pong kernel where there are >= 256 tiles of 256 x 160 (every level-0 linear / convolution at batch 8), or of 256 x 128
-    //     where N is not a multiple of 160 (VAE decoder); the GEGLU projection (value | gate pairs) from K = 1280 up, or K = 640 with
-    //     at least 8192 rows;
-    //   * loader / consumer kernel where 128- or 64-row tiles give 200...256 workgroups (with K slices where K is deep): conv 32x32
-    //     640->640 at batch 8 72.8 -> 55.5 us, 64x64 320->320 at batch 4 41.3 -> 33.0 us, linear M=2048 N=1280 K=5120 49.4 -> 36.8 us.
-    //     More than 256 such tiles would run in two rounds of one workgroup per CU, fewer than ~200 leave CUs idle: both keep the
-    //     plans above.
-    // CO-RUNNING FAMILY (gmd_gemm_plan_family(1); what the dual-UNet pipeline selects for its two overlapped forwards) -- the largest
-    // tile, filled up with K slices: slower launch by launch, faster on the wall of the two-stream pipeline in every interleaved
-    // whole-run A/B (profiles/r05_ab_plan_default.txt, five rounds on one box: 867.7 -> 849.0 ms per batch at batch 4 (-2.2 %, 5 of 5),
-    // 1454.3 -> 1436.9 at batch 8 (-1.2 %, 3 of 3); round 4, three boxes: -0.4 ... -1.3 %).  With two streams in flight a second
-    // workgroup is always there to hide a kernel's own latencies, so L2 -> LDS bytes per product -- (1/BM + 1/BN) x 2 B: 0.020 for a
-    // 256 x 160 tile, 0.028 for 128 x 160, 0.044 for 64 x 160 -- weigh more than the launch's time alone on the chip.  With the
-    // streams serialised the same family LOSES 8.6 % (1018.3 -> 1106.3 ms), so it is never the choice of a launch that runs alone:
-    // family 0 stays the default of the C ABI.  GMD_PP=0: the round-3 plans.
-    if (g_pp_enabled && batch == 1 && !(fbm && fbn) && !fpf && !fks && M >= 64) {
-        const int64_t mt256 = (M + 255) / 256;
-        const int bn = N % 160 == 0 ? 160 : (N % 128 == 0 ? 128 : 0);
-        if (big_tiles()) {
-            if (pair_tiles) {
-                if (M >= 256 && N % 128 == 0) pl = Plan{256, 128, 283, 1};  // GEGLU pairs value / gate tiles: no K slices
-            } else if (bn && M >= 256) {
-                auto slices = [&](int bnc) {
-                    const int64_t t = mt256 * (N / bnc);
-                    int ks = t >= g_f1_target ? 1 : (int)((g_f1_target + t / 2) / t);
-                    if (ks > 8) ks = 8;
-                    while (ks > 1 && (nk / ks < g_f1_min_steps || (int64_t)ks * M * N * (int64_t)sizeof(float) > ws_bytes)) --ks;
-                    return ks;
-                };
-                int bnc = bn;
-                // 128-column tiles where they still fit ONE round of workgroups: their row segments are whole 128-byte lines (a
-                // 160-column tile shares every third line of a row with its neighbour) and there are a quarter more of them
-                // (not for a launch that is to emit GroupNorm statistics: their 10-channel buckets need 80-column wave tiles)
-                if (g_f1_bn128 && !want_cs && bn == 160 && N % 128 == 0 && mt256 * (N / 128) * slices(128) <= 256) bnc = 128;
-                pl = Plan{256, bnc, 283, slices(bnc)};
-            }
-        } else if (pair_tiles) {
-            if (M >= 256 && N % 128 == 0 && ((nk >= 20 && M >= 512) || (nk >= 10 && M >= 8192))) pl = Plan{256, 128, 283, 1};
-        } else if (bn && M >= 256 && mt256 * (N / bn) >= 256) {
-            pl = Plan{256, bn, 283, 1};
-        } else if (bn) {
-            bool found = false;
-            for (int bm = 128; bm >= 64 && !found; bm >>= 1) {  // unsplit first: the larger tile wins when both fill the chip
-                const int64_t t = (int64_t)((M + bm - 1) / bm) * (N / bn);
-                if (t >= 200 && t <= 256) { pl = Plan{bm, bn, 244, 1}; found = true; }
-            }
-            // 64-row tiles pull 28 KB per K step through the CU for half the products of a 128-row tile (36 KB): with a deep K two
-            // slices of 128-row tiles beat them (tools/sweep_lc.py, conv 16x16 1280->1280 at batch 8: 78.2 -> 66.9 us, 2560->1280:
-            // 155 -> 121 us; at K = 5760 the slab reduction costs more than it buys: 39.4 vs 42.1 us)
-            if (found && pl.bm == 64 && nk >= 144 && 2 * (int64_t)M * N * (int64_t)sizeof(float) <= ws_bytes) {
-                const int64_t t = (int64_t)((M + 127) / 128) * (N / bn) * 2;
-                if (t >= 200 && t <= 256) pl = Plan{128, bn, 244, 2};
-            }
-            for (int bm = 128; bm >= 64 && !found; bm >>= 1) {  // K slices: at least 20 K steps (K = 1280) each
-                const int64_t t = (int64_t)((M + bm - 1) / bm) * (N / bn);
-                for (int ks = 2; ks <= 8 && !found; ++ks)
-                    if (t * ks >= 200 && t * ks <= 256 && nk / ks >= 20 && (int64_t)ks * M * N * (int64_t)sizeof(float) <= ws_bytes) {
-                        pl = Plan{bm, bn, 244, ks};
-                        found = true;
-                    }
-            }
-            // still nothing (the GM UNet's 16x16 projections at batch 4, M = 1024 N = K = 1280: 128 tiles of 64 x 160, K too short to
-            // slice): 64 x 128 loader / consumer tiles, a quarter more workgroups than 64 x 160 (tools/dbg/sweep_rows.py: 13.7 us on the
-            // legacy 64 x 64 kernel -> 11.3 us; the vendor library 11.5)
-            if (!found && !want_cs && N % 128 == 0 && nk >= 8) {  // (validated for K >= 512 only)
-                const int64_t t = (int64_t)((M + 63) / 64) * (N / 128);
-                if (t >= 144 && t <= 256) pl = Plan{64, 128, 244, 1};
-            }
-        }
-    }
-    return pl;
-}
-
 template <typename HT, bool CONV, int BM, int BN, int PF>
 hipError_t launch_bf16(const GemmParams& p, int gz, hipStream_t s) {
     constexpr size_t smem = 2 * (BM + BN) * 128;
@@ -2520,18 +2311,8 @@ hipError_t launch_lc(const GemmParams& p, int gz, hipStream_t s) {
     return hipGetLastError();
 }
 
-// conv_patch_kernel: stride-1 / pad-1 convolutions whose 256-pixel tiles are whole image rows (or whole images) -- every UNet level
-bool conv_patch_ok(const GemmParams& p) {
-    const int H = p.Hin, W = p.Win, HW = H * W;
-    if (p.stride != 1 || p.upsample || p.pad_lo != 1 || p.Hout != H || p.Wout != W) return false;
-    if (W < 8 || W > 64 || (W & (W - 1)) || p.Cin % BK || p.M % HW) return false;
-    if (HW >= 256 ? (HW % 256 != 0) : (256 % HW != 0)) return false;
-    const int R = HW >= 256 ? 256 / W : H, nimg = 256 / (R * W);
-    return nimg * (R + 2) * (W + 2) <= 400;
-}
-
 template <typename HT, int TN>
-hipError_t launch_conv_patch(const GemmParams& p, int gz, hipStream_t s) {
+hipError_t launch_conv_patch(const GemmParams& p, bool continuous, int gz, hipStream_t s) {
     constexpr int BM = 256, BN = 2 * TN * 16;
     const int H = p.Hin, W = p.Win, HW = H * W;
     const int R = HW >= 256 ? 256 / W : H, nimg = 256 / (R * W);
@@ -2541,7 +2322,7 @@ hipError_t launch_conv_patch(const GemmParams& p, int gz, hipStream_t s) {
     const size_t need = smem > strips ? smem : strips;
     dim3 grid(((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM), 1, gz);
     hipError_t e;
-    if (g_conv_patch_mode == 2) {
+    if (continuous) {
         if (npieces > 44) {
             e = opt_in_lds(reinterpret_cast<const void*>(&conv_patch_cont_kernel<HT, TN, 13>), 163840);
             if (e != hipSuccess) return e;
@@ -2576,89 +2357,20 @@ hipError_t launch_pp(const GemmParams& p, int gz, hipStream_t s) {
     return hipGetLastError();
 }
 
-// One 16-bit element type (bf16_t or f16_t): plan, kernel choice, split-K reduction.  float16 instantiates the kernels the
-// heuristic actually picks; the register-staged and deeper-ring tuning variants exist for bfloat16 only (plan overrides).
-// Column statistics (GemmParams::colstats) come out of the row epilogue of the default ring kernels only: every tile must be a
-// full tile of a single, unsplit launch whose waves own 64 rows x (BN/2) columns, a whole number of buckets.
-// A split-K launch reduces inside the kernel (splitk_fixup) when this holds; `ws_bytes` = usable workspace bytes.  The one predicate
-// of the launch itself (launch_half) and of the plan queries that depend on it (column statistics).
-bool fixup_plan_ok(const Plan& pl, int M, int N, int64_t ws_bytes, bool defer_reduce) {
-    if (pl.ksplit <= 1 || pl.ksplit > g_fixup_max || defer_reduce || ws_bytes <= 0 || !(pl.pf == 283 || pl.pf == 244)) return false;
-    const int64_t tiles = (int64_t)((N + pl.bn - 1) / pl.bn) * ((M + pl.bm - 1) / pl.bm);
-    const int64_t frag_bytes = (int64_t)(pl.ksplit - 1) * tiles * pl.bm * pl.bn * 4;
-    return tiles <= kFixupCounters && frag_bytes <= ws_bytes && frag_bytes < 0xFFFF0000LL;
-}
-
-// (split launches: the finisher of the in-kernel reduction runs the row epilogue of an unsplit launch, statistics included)
-bool colstats_plan_ok(const Plan& pl, int M, int N, int batch, int bucket, int64_t ws_bytes) {
-    // all three: waves own 64 rows x (BN/2) columns
-    const bool ring = pl.pf == 0 && pl.bm == 128, pp = pl.pf == 283 && pl.bm == 256, lc = pl.pf == 244 && pl.bm == 128;
-    return (ring || pp || lc) && (pl.bn == 160 || pl.bn == 128) && (pl.ksplit == 1 || fixup_plan_ok(pl, M, N, ws_bytes, false)) && batch == 1 &&
-           bucket > 0 && M % pl.bm == 0 && N % pl.bn == 0 && (pl.bn / 2) % bucket == 0;
-}
-
-// The one place that refuses a plan (heuristic or forced) whose kernel lacks an epilogue the launch asks for; nullptr = fine.
-//   * GEGLU pairs value / gate tiles of 16 columns inside a wave: only kernels with an EVEN number of column tiles per wave
-//     implement it (128x128 and 64x64 register / DMA kernels, ring tiles with TN = 2 or 4) and never with split-K -- any
-//     other kernel's plain epilogue would store [M, N] into the [M, N/2] output;
-//   * column statistics come out of the full-tile row epilogue of the two default 128-row ring kernels only.
-const char* plan_unsupported(const Plan& pl, const GemmParams& p, int batch, int64_t ws_bytes) {
-    if (p.act == GMD_ACT_GEGLU) {
-        const bool odd_tn = pl.bn == 160 || (pl.pf >= 100 && pl.pf != 283 && pl.bm == 64 && pl.bn == 64);  // TN = 5 / ring<1,4,1,.>: TN = 1
-        if (odd_tn || pl.ksplit > 1 || p.out_f32 || (pl.pf == 244 && pl.bm != 128)) return "has no GEGLU epilogue";
-    }
-    if (p.colstats) {
-        const bool rows_ok = !p.out_f32 && p.act != GMD_ACT_GEGLU && (p.ldc & 7) == 0 && (p.residual == nullptr || (p.ldr & 7) == 0) &&
-                             (p.rowbias == nullptr || ((p.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0));
-        if (!rows_ok || p.defer_reduce || !colstats_plan_ok(pl, p.M, p.N, batch, p.cs_bucket, ws_bytes))
-            return "cannot emit column statistics (they need the full-tile row epilogue of an unsplit 128-row ring launch: ask "
-                   "gmd_gemm_colstats_plan first)";
-    }
-    return nullptr;
-}
-
-// Tile order of the ping-pong / loader-consumer kernels (GemmParams::tile_group).  Workgroups with equal id % 8 share an XCD and get
-// a contiguous run of tiles; with n fastest an XCD walks whole M-panels, so between two uses of a weight tile lie all the others:
-//   * weights larger than the activations (N > M: the GEGLU projections of the 16x16 / 8x8 levels, W up to 26 MB): m fastest --
-//     each weight tile then goes to ONE XCD instead of all eight (rocprofv3 FETCH_SIZE, M=2048 N=10240 K=1280: 226 MB = 7.2x the
-//     algorithmic reads with n fastest);
-//   * activations larger, but the weights do not fit an XCD's 4 MiB L2 beside them (M=8192 N=5120 K=640: W = 6.5 MB, 231 MB fetched
-//     = 13.6x): the XCD's M-panels are walked together, one N tile at a time, so every weight tile is fetched once per XCD.
-// Everything else keeps n fastest.
-int pick_tile_group(const Plan& pl, int M, int N, int K) {
-    if (pl.pf != 283 && pl.pf != 244) return 1;
-    const int tiles_m = (M + pl.bm - 1) / pl.bm;
-    const int64_t w_bytes = (int64_t)N * K * 2;
-    int g;
-    if (N > M) g = tiles_m;
-    else if (w_bytes <= (3ll << 20)) return 1;
-    else g = (tiles_m + 7) / 8;  // the XCD's share of M-panels
-    // Round 5: at most FOUR M-panels per group.  An XCD walks its run of tiles one W panel at a time over the group's A panels: the
-    // A panels must survive in its 4 MiB L2 beside the W panels in flight and the output lines passing through, the W panels are
-    // streamed once.  rocprofv3 FETCH_SIZE against the group (profiles/r05_pmc_tile_group.txt, MB read, algorithmic in brackets):
-    // M=4096 N=5120 K=640 [11.8]: 16 (the N > M rule) 126, 8: 50, 4: 37.5, 2: 59;  M=2048 N=10240 K=1280 [31.5]: 8 (N > M) 145, 4: 110,
-    // 2: 130;  M=8192 N=5120 K=640 [17]: 4 (the share rule) 66, 8: 84, 2: 121;  M=1024 N=10240 K=1280: 4 = all its panels, 63.
-    if (g > 4) g = 4;
-    return g < 1 ? 1 : g;
-}
-
-// fused Q|K|V projection with transposed V tiles (GemmParams::vt_out, epilogue_cols_vt): every tile full and through the row epilogue,
-// the V columns starting on a tile boundary, wave tiles (64 or 32 rows) inside one sample
-bool qkv_vt_plan_ok(const Plan& pl, int M, int N, int batch, int vt_col0, int vt_tokens) {
-    return batch == 1 && pl.ksplit == 1 && M % pl.bm == 0 && N % pl.bn == 0 && vt_col0 > 0 && vt_col0 < N && vt_col0 % pl.bn == 0 &&
-           vt_tokens > 0 && vt_tokens % 64 == 0 && M % vt_tokens == 0;
-}
-
+// One 16-bit element type (bf16_t or f16_t): the plan (gemm_plan.cpp), kernel choice, split-K reduction.  float16 instantiates the
+// kernels the heuristic actually picks; the register-staged and deeper-ring tuning variants exist for bfloat16 only (plan overrides).
 template <typename HT, bool CONV>
 int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
     constexpr bool kTune = std::is_same<HT, bf16_t>::value;
     hipError_t e = hipSuccess;
-    const Plan pl = make_plan(p.M, p.N, p.K, batch, ws ? ws_bytes : 0, p.act == GMD_ACT_GEGLU, p.colstats != nullptr);
+    const PlanConfig cfg = plan_config();
+    const int64_t usable = ws ? ws_bytes : 0;
+    const Plan pl = make_plan(cfg, p.M, p.N, p.K, batch, usable, p.act == GMD_ACT_GEGLU, p.colstats != nullptr);
     if (p.vt_out && !qkv_vt_plan_ok(pl, p.M, p.N, batch, p.vt_col0, p.vt_tokens)) {
         gmd_set_error("%s: plan %dx%d ksplit=%d cannot write transposed V tiles (ask gmd_gemm_qkv_vt_ok first)", name, pl.bm, pl.bn, pl.ksplit);
         return GMD_ERR_UNSUPPORTED;
     }
-    if (const char* why = plan_unsupported(pl, p, batch, ws ? ws_bytes : 0)) {
+    if (const char* why = plan_unsupported(cfg, pl, p, batch, usable)) {
         gmd_set_error("%s: plan %dx%d pf=%d ksplit=%d (M=%d N=%d bucket=%d) %s", name, pl.bm, pl.bn, pl.pf, pl.ksplit, p.M, p.N, p.cs_bucket, why);
         return GMD_ERR_UNSUPPORTED;
     }
@@ -2666,31 +2378,27 @@ int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t
     p.ws = (float*)ws;
     p.tile_group = CONV ? 1 : pick_tile_group(pl, p.M, p.N, p.K);  // (convolutions: neighbouring M-panels share their halo rows)
     const int gz = pl.ksplit > 1 ? pl.ksplit : batch;
-    // In-kernel split-K reduction (splitk_fixup) instead of slabs + splitk_reduce_kernel: the round-4 kernels (one workgroup per CU,
-    // wave tiles in registers), up to g_fixup_max slices (the finisher reads the other slices' fragments one after the other), the
-    // consumer of the slabs not being a fused GroupNorm (defer_reduce).  Bit-identical to the slab path (same order of additions).
     p.fixup = 0;
-    if (fixup_plan_ok(pl, p.M, p.N, ws ? ws_bytes : 0, p.defer_reduce != 0)) {
-        const int64_t tiles = (int64_t)((p.N + pl.bn - 1) / pl.bn) * ((p.M + pl.bm - 1) / pl.bm);
+    if (fixup_plan_ok(cfg, pl, p.M, p.N, usable, p.defer_reduce != 0)) {  // in-kernel split-K reduction instead of slabs + splitk_reduce_kernel
         p.fixup = 1;
-        p.fix_bytes = (unsigned)((int64_t)(pl.ksplit - 1) * tiles * pl.bm * pl.bn * 4);
+        p.fix_bytes = (unsigned)fixup_bytes(pl, p.M, p.N);
         p.fix_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + ws_bytes);  // the tail behind the usable bytes
     }
     bool done = false;
-    if (pl.pf == 244) {  // loader / consumer kernel: 4 consumer + 4 loader waves, 4-stage ring, one workgroup per CU
+    if (pl.pf == kLoaderConsumer) {  // loader / consumer kernel: 4 consumer + 4 loader waves, 4-stage ring, one workgroup per CU
         if (pl.bm == 128 && pl.bn == 160) e = launch_lc<HT, CONV, 4, 5>(p, gz, s);
         else if (pl.bm == 128 && pl.bn == 128) e = launch_lc<HT, CONV, 4, 4>(p, gz, s);
         else if (pl.bm == 64 && pl.bn == 160) e = launch_lc<HT, CONV, 2, 5>(p, gz, s);
         else if (pl.bm == 64 && pl.bn == 128) e = launch_lc<HT, CONV, 2, 4>(p, gz, s);
         else { gmd_set_error("%s: loader/consumer tile %dx%d is not instantiated", name, pl.bm, pl.bn); return GMD_ERR_UNSUPPORTED; }
         done = true;
-    } else if (CONV && pl.pf == 283 && g_conv_patch_mode != 0 && conv_patch_ok(p) && (int64_t)pl.ksplit <= p.Cin / BK) {
+    } else if (CONV && use_conv_patch(cfg, pl, p)) {
         // ping-pong structure with the input patch resident in LDS (conv_patch_kernel): same tiles, same epilogues, same plan code
-        if (pl.bn == 160) e = launch_conv_patch<HT, 5>(p, gz, s);
-        else if (pl.bn == 128) e = launch_conv_patch<HT, 4>(p, gz, s);
+        if (pl.bn == 160) e = launch_conv_patch<HT, 5>(p, cfg.conv_patch_mode == 2, gz, s);
+        else if (pl.bn == 128) e = launch_conv_patch<HT, 4>(p, cfg.conv_patch_mode == 2, gz, s);
         else { gmd_set_error("%s: ping-pong tile %dx%d is not instantiated", name, pl.bm, pl.bn); return GMD_ERR_UNSUPPORTED; }
         done = true;
-    } else if (pl.pf == 283) {  // ping-pong kernel: 8 consumer + 4 loader waves on a 256-row tile
+    } else if (pl.pf == kPingPong) {  // ping-pong kernel: 8 consumer + 4 loader waves on a 256-row tile
         if (pl.bm == 256 && pl.bn == 160) e = launch_pp<HT, CONV, 5>(p, gz, s);
         else if (pl.bm == 256 && pl.bn == 128) e = launch_pp<HT, CONV, 4>(p, gz, s);
         else { gmd_set_error("%s: ping-pong tile %dx%d is not instantiated", name, pl.bm, pl.bn); return GMD_ERR_UNSUPPORTED; }
@@ -2710,15 +2418,15 @@ int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t
         else if (pl.pf == 104 && pl.bm == 64 && pl.bn == 64) e = launch_ring<HT, CONV, 1, 4, 1, 4>(p, gz, s);
         else if (pl.pf == 103 && pl.bm == 64 && pl.bn == 128) e = launch_ring<HT, CONV, 1, 4, 2, 3>(p, gz, s);
         else if (pl.pf == 104 && pl.bm == 64 && pl.bn == 128) e = launch_ring<HT, CONV, 1, 4, 2, 4>(p, gz, s);
-        else if (pl.pf >= 100) { gmd_set_error("%s: ring variant %d not instantiated for BN=%d", name, pl.pf, pl.bn); return GMD_ERR_UNSUPPORTED; }
-        else if (pl.pf != 0 && pl.bm == 128 && pl.bn == 160)
-            e = pl.pf == 1 ? launch_bf16<HT, CONV, 128, 160, 1>(p, gz, s) : launch_bf16<HT, CONV, 128, 160, 2>(p, gz, s);
-        else if (pl.pf != 0 && pl.bm == 128 && pl.bn == 128)
-            e = pl.pf == 1 ? launch_bf16<HT, CONV, 128, 128, 1>(p, gz, s) : launch_bf16<HT, CONV, 128, 128, 2>(p, gz, s);
-        else if (pl.pf != 0 && !(pl.bm == 128))
-            e = pl.pf == 1 ? launch_bf16<HT, CONV, 64, 64, 1>(p, gz, s) : launch_bf16<HT, CONV, 64, 64, 2>(p, gz, s);
+        else if (is_ring_variant(pl.pf)) { gmd_set_error("%s: ring variant %d not instantiated for BN=%d", name, pl.pf, pl.bn); return GMD_ERR_UNSUPPORTED; }
+        else if (pl.pf != kRing && pl.bm == 128 && pl.bn == 160)
+            e = pl.pf == kRegStaged1 ? launch_bf16<HT, CONV, 128, 160, 1>(p, gz, s) : launch_bf16<HT, CONV, 128, 160, 2>(p, gz, s);
+        else if (pl.pf != kRing && pl.bm == 128 && pl.bn == 128)
+            e = pl.pf == kRegStaged1 ? launch_bf16<HT, CONV, 128, 128, 1>(p, gz, s) : launch_bf16<HT, CONV, 128, 128, 2>(p, gz, s);
+        else if (pl.pf != kRing && !(pl.bm == 128))
+            e = pl.pf == kRegStaged1 ? launch_bf16<HT, CONV, 64, 64, 1>(p, gz, s) : launch_bf16<HT, CONV, 64, 64, 2>(p, gz, s);
         else done = false;
-    } else if (pl.pf != 0 && pl.pf != 283 && pl.pf != 244) {
+    } else if (pl.pf != kRing) {
         gmd_set_error("%s: plan override pf=%d is instantiated for bfloat16 only", name, pl.pf);
         return GMD_ERR_UNSUPPORTED;
     }
@@ -2768,76 +2476,6 @@ int launch(GemmParams p, int dtype, int batch, void* ws, int64_t ws_bytes, hipSt
 
 extern "C" {
 
-int gmd_gemm_plan_override(int bm, int bn, int pf, int ksplit) {
-    GMD_REQUIRE(bm >= 0 && bn >= 0 && pf >= 0 && ksplit >= 0, "gmd_gemm_plan_override: negative value");
-    if (!tuning_enabled() && (bm | bn | pf | ksplit) != 0) {
-        gmd_set_error("gmd_gemm_plan_override: kernel-tuning overrides are a debug facility; set GMD_TUNING=1 in the environment to use them");
-        return GMD_ERR_UNSUPPORTED;
-    }
-    g_force.bm = bm; g_force.bn = bn; g_force.pf = pf; g_force.ks = ksplit;
-    // the float32 matrix-core path has its own planner (gemm_split.hip); of an override it takes the kernel family only:
-    // pf 244 = its loader / converter kernel wherever instantiated, anything else = its default (the in-register split)
-    gmd_split_set_lc(pf == 244 ? 1 : 0);
-    return GMD_OK;
-}
-
-int gmd_gemm_plan_family(int family) {
-    const int prev = t_plan_family;
-    if (family == 0 || family == 1) t_plan_family = family;  // anything else: query only
-    return prev;
-}
-
-int gmd_splitk_fixup_max(int max_slices) {
-    const int prev = g_fixup_max;
-    if (max_slices >= 0) g_fixup_max = max_slices > 16 ? 16 : max_slices;
-    return prev;
-}
-
-int gmd_conv_patch_override(int mode) {
-    GMD_REQUIRE(mode >= 0 && mode <= 2, "gmd_conv_patch_override: mode 0, 1 or 2");
-    if (!tuning_enabled()) {
-        gmd_set_error("gmd_conv_patch_override: kernel-tuning overrides are a debug facility; set GMD_TUNING=1 in the environment to use them");
-        return GMD_ERR_UNSUPPORTED;
-    }
-    g_conv_patch_mode = mode;
-    return GMD_OK;
-}
-
-int gmd_gemm_colstats_plan(int dtype, int M, int N, int K, int batch, int64_t workspace_bytes, int bucket) {
-    workspace_bytes = gmd_ws_usable_bytes(workspace_bytes);  // the tail of the workspace holds the split-K arrival counters
-    if (gmd_is_split(dtype)) return gmd_split_colstats_ok(M, N, K, batch, workspace_bytes, bucket);  // round 4
-    if (!gmd_is_half(dtype) || M <= 0 || N <= 0 || K <= 0 || K % BK != 0) return 0;
-    return colstats_plan_ok(make_plan(M, N, K, batch, workspace_bytes, false, true), M, N, batch, bucket, workspace_bytes) ? 1 : 0;
-}
-
-int gmd_gemm_plan_info(int dtype, int M, int N, int K, int batch, int64_t workspace_bytes, int geglu, int* out4) {
-    workspace_bytes = gmd_ws_usable_bytes(workspace_bytes);  // the tail of the workspace holds the split-K arrival counters
-    GMD_REQUIRE(gmd_is_half(dtype) && M > 0 && N > 0 && K > 0 && K % BK == 0 && batch > 0 && out4, "gmd_gemm_plan_info: 16-bit launches only");
-    const Plan pl = make_plan(M, N, K, batch, workspace_bytes, geglu != 0);
-    out4[0] = pl.bm; out4[1] = pl.bn; out4[2] = pl.pf; out4[3] = pl.ksplit;
-    return GMD_OK;
-}
-
-// K slices of a float32 matrix-core (GMD_F32S / GMD_F32SW / GMD_F32SA) gmd_gemm_nt launch: slabs + splitk_reduce_f32_kernel when > 1
-int gmd_split_plan_ksplit(int M, int N, int K, int64_t workspace_bytes) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32) return 0;
-    return gmd_split_plan_ksplit_usable(M, N, K, gmd_ws_usable_bytes(workspace_bytes));
-}
-
-// 1 when a float32-split gmd_gemm_nt launch of these dimensions can take out_dtype = GMD_F32SA (store its result pre-split)
-int gmd_gemm_out_split_ok(int M, int N, int K, int geglu, int64_t workspace_bytes) { return gmd_split_out_ok(M, N, K, geglu, gmd_ws_usable_bytes(workspace_bytes)); }
-
-// (ws_bytes: the USABLE bytes, i.e. without the counter tail)
-static int qkv_vt_ok_usable(int dtype, int M, int N, int K, int vt_col0, int vt_tokens, int64_t ws_bytes) {
-    if (dtype == GMD_F32SW || dtype == GMD_F32SA) return gmd_split_qkv_vt_ok(M, N, K, vt_col0, vt_tokens, ws_bytes);
-    if (!gmd_is_half(dtype) || M <= 0 || N <= 0 || K <= 0 || K % 64) return 0;
-    return qkv_vt_plan_ok(make_plan(M, N, K, 1, ws_bytes, false), M, N, 1, vt_col0, vt_tokens) ? 1 : 0;
-}
-
-int gmd_gemm_qkv_vt_ok(int dtype, int M, int N, int K, int vt_col0, int vt_tokens, int64_t workspace_bytes) {
-    return qkv_vt_ok_usable(dtype, M, N, K, vt_col0, vt_tokens, gmd_ws_usable_bytes(workspace_bytes));
-}
-
 int gmd_gemm_qkv_vt(const void* A, const void* W, void* C, void* Vt, int dtype, int M, int N, int K, int64_t ldc, int vt_col0, int vt_tokens,
                     int64_t vt_ld, float alpha, void* workspace, int64_t workspace_bytes, gmd_stream_t stream) {
     workspace_bytes = gmd_ws_usable_bytes(workspace_bytes);  // the tail of the workspace holds the split-K arrival counters
@@ -2850,7 +2488,7 @@ int gmd_gemm_qkv_vt(const void* A, const void* W, void* C, void* Vt, int dtype, 
     // pre-split operands are [hi 64 B | lo 64 B] per 32-element chunk of a row (rows are K elements here): whole 128-byte chunks only
     GMD_REQUIRE(!split || ((reinterpret_cast<uintptr_t>(W) & 127) == 0 && (dtype != GMD_F32SA || (reinterpret_cast<uintptr_t>(A) & 127) == 0)),
                 "gmd_gemm_qkv_vt: a pre-split operand must be 128-byte aligned (32-element chunks of [hi | lo])");
-    GMD_REQUIRE(qkv_vt_ok_usable(dtype, M, N, K, vt_col0, vt_tokens, workspace ? workspace_bytes : 0), "gmd_gemm_qkv_vt: this launch cannot write transposed V tiles (ask gmd_gemm_qkv_vt_ok)");
+    GMD_REQUIRE(qkv_vt_ok(plan_config(), dtype, M, N, K, vt_col0, vt_tokens, workspace ? workspace_bytes : 0), "gmd_gemm_qkv_vt: this launch cannot write transposed V tiles (ask gmd_gemm_qkv_vt_ok)");
     GemmParams p{};
     p.A = A; p.W = W; p.C = C; p.M = M; p.N = N; p.K = K;
     p.lda = K; p.ldw = K; p.ldc = ldc;
@@ -2864,7 +2502,7 @@ int gmd_gemm_qkv_vt(const void* A, const void* W, void* C, void* Vt, int dtype, 
     p.vt_out = Vt; p.vt_col0 = vt_col0; p.vt_tokens = vt_tokens; p.vt_ld = vt_ld;
     if (split) {
         p.out_f32 = 1;
-        return gmd_launch_split_gemm(&p, dtype == GMD_F32SA ? 2 : 1, 1, workspace, workspace_bytes, (hipStream_t)stream, "gmd_gemm_qkv_vt");
+        return gmd_launch_split_gemm(p, dtype == GMD_F32SA ? 2 : 1, 1, workspace, workspace_bytes, (hipStream_t)stream, "gmd_gemm_qkv_vt");
     }
     return launch<false>(p, dtype, 1, workspace, workspace_bytes, (hipStream_t)stream, "gmd_gemm_qkv_vt");
 }
@@ -2882,7 +2520,7 @@ int gmd_gemm_nt(const void* A, const void* W, void* C, int dtype, int out_dtype,
     GMD_REQUIRE(M >= 0 && N >= 0 && K > 0 && batch >= 0, "gmd_gemm_nt: bad shape M=%d N=%d K=%d batch=%d", M, N, K, batch);
     if (c_split) {  // full 128-row tiles through the row epilogues only: the caller asks gmd_gemm_out_split_ok first
         const int nout = act == GMD_ACT_GEGLU ? N / 2 : N;
-        GMD_REQUIRE(batch == 1 && nout % 32 == 0 && ldc == nout && !colstats && gmd_split_out_ok(M, N, K, act == GMD_ACT_GEGLU, workspace ? workspace_bytes : 0),
+        GMD_REQUIRE(batch == 1 && nout % 32 == 0 && ldc == nout && !colstats && f32_out_ok(M, N, K, act == GMD_ACT_GEGLU, workspace ? workspace_bytes : 0),
                     "gmd_gemm_nt: this launch cannot store its output pre-split (ask gmd_gemm_out_split_ok; ldc must equal the row length)");
     }
     if (M == 0 || N == 0 || batch == 0) return GMD_OK;
@@ -2927,7 +2565,7 @@ int gmd_gemm_nt(const void* A, const void* W, void* C, int dtype, int out_dtype,
     p.cblk = K;
     p.colstats = colstats; p.cs_bucket = colstats_bucket;
     if (split) {
-        return gmd_launch_split_gemm(&p, dtype == GMD_F32SA ? 2 : dtype == GMD_F32SW ? 1 : 0, batch, batch == 1 ? workspace : nullptr, workspace_bytes,
+        return gmd_launch_split_gemm(p, dtype == GMD_F32SA ? 2 : dtype == GMD_F32SW ? 1 : 0, batch, batch == 1 ? workspace : nullptr, workspace_bytes,
                                      (hipStream_t)stream, "gmd_gemm_nt");
     }
     return launch<false>(p, dtype, batch, workspace, workspace_bytes, (hipStream_t)stream, "gmd_gemm_nt");
@@ -2946,32 +2584,6 @@ struct GnTail {
     const float* beta;
     int silu;
 };
-
-// `upsample`: 0, 1 (nearest 2x) or GMD_UPSAMPLE_TO(Hout, Wout) (nearest to a given size; include/gmd_hip.h).  False (message left
-// for the caller's error) when the requested size is not one a stride-2 level can have come from: Hout in {2 Hin - 1, 2 Hin}.  For
-// those two torch's nearest map with size= is dst >> 1, as for 2x: only the bound of the virtual image moves (the kernels test
-// uy >= Hout), and Hout <= 2 Hin keeps uy >> 1 inside the source.  `upsample` leaves as 0 / 1.
-bool conv_out_shape(int Hin, int Win, int stride, int& upsample, int pad_mode, int& Hout, int& Wout, int& pad_lo) {
-    if (upsample == 1) { Hout = 2 * Hin; Wout = 2 * Win; pad_lo = 1; }
-    else if (upsample) {
-        Hout = upsample >> 16; Wout = upsample & 0xFFFF; pad_lo = 1;
-        if (upsample < 0 || !(Hout == 2 * (int64_t)Hin - 1 || Hout == 2 * (int64_t)Hin) || !(Wout == 2 * (int64_t)Win - 1 || Wout == 2 * (int64_t)Win)) {
-            gmd_set_error("gmd_conv3x3: upsample to %dx%d from %dx%d: each output side must be 2*in - 1 or 2*in", Hout, Wout, Hin, Win);
-            return false;
-        }
-        upsample = 1;
-    }
-    else if (pad_mode == 1) { Hout = (Hin + 1 - 3) / 2 + 1; Wout = (Win + 1 - 3) / 2 + 1; pad_lo = 0; }
-    else { Hout = (Hin + 2 - 3) / stride + 1; Wout = (Win + 2 - 3) / stride + 1; pad_lo = 1; }
-    return true;
-}
-
-// split-K factor the conv launch will use (1 = unsplit); the same planners the launch itself calls
-int conv_plan_ksplit(int dtype, int64_t M, int Cin, int Cout, int64_t ws_bytes) {
-    if (gmd_is_split(dtype)) return gmd_split_plan_ksplit_usable((int)M, Cout, 9 * Cin, ws_bytes);
-    if (gmd_is_half(dtype)) return make_plan((int)M, Cout, 9 * Cin, 1, ws_bytes, false).ksplit;
-    return 1;
-}
 
 int conv3x3_impl(const void* X, const void* Wt, void* Y, int dtype, int out_dtype, int B, int Hin, int Win, int Cin, int Cout,
                  int stride, int upsample, int pad_mode, const float* bias, const float* rowbias, int64_t ldrb, const void* residual,
@@ -3009,19 +2621,20 @@ int conv3x3_impl(const void* X, const void* Wt, void* Y, int dtype, int out_dtyp
     p.residual = residual; p.ldr = Cout; p.alpha = alpha; p.act = GMD_ACT_NONE;
     p.out_f32 = out_dtype == GMD_F32;
     p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.upsample = upsample; p.pad_lo = pad_lo;
-    p.cblk = conv_channel_block(B, Hin, Win, Cin, Cout, dtype);
+    const PlanConfig cfg = plan_config();
+    p.cblk = conv_channel_block(cfg, B, Hin, Win, Cin, Cout, dtype);
     p.colstats = colstats; p.cs_bucket = colstats_bucket;
     int ks = 1;
     if (gn) {  // the split-K slabs stay in the workspace; the GroupNorm kernel sums them (no reduce launch, no raw tensor unless Y)
         const int act_dtype = split ? GMD_F32 : dtype;
-        ks = workspace ? conv_plan_ksplit(dtype, M, Cin, Cout, workspace_bytes) : 1;
+        ks = workspace ? conv_plan_ksplit(cfg, dtype, M, Cin, Cout, workspace_bytes) : 1;
         if (ks <= 1 || colstats || out_dtype != act_dtype || !gmd_gn_from_slabs_ok(act_dtype, B, (int64_t)Hout * Wout, Cout, gn->G)) {
             gmd_set_error("gmd_conv3x3_groupnorm: this launch does not fuse (split-K factor %d; ask gmd_conv3x3_gn_fusable first)", ks);
             return GMD_ERR_UNSUPPORTED;
         }
         p.defer_reduce = 1;
     }
-    const int rc = split ? gmd_launch_split_conv(&p, dtype == GMD_F32SA ? 2 : dtype == GMD_F32SW ? 1 : 0, B, workspace, workspace_bytes, (hipStream_t)stream, "gmd_conv3x3")
+    const int rc = split ? gmd_launch_split_conv(p, dtype == GMD_F32SA ? 2 : dtype == GMD_F32SW ? 1 : 0, workspace, workspace_bytes, (hipStream_t)stream, "gmd_conv3x3")
                          : launch<true>(p, dtype, 1, workspace, workspace_bytes, (hipStream_t)stream, "gmd_conv3x3");
     if (rc != GMD_OK || !gn) return rc;
     return gmd_launch_gn_from_slabs((const float*)workspace, ks, alpha, bias, rowbias, p.ldrb, residual, Y, gn->Ynorm, split ? GMD_F32 : dtype, B,
@@ -3052,7 +2665,7 @@ int gmd_conv3x3_gn_fusable(int dtype, int B, int Hin, int Win, int Cin, int Cout
     // one workgroup per (sample, group) walks all slabs of its slice: below one workgroup per CU the separate, fully parallel
     // reduction wins (tools/bench_conv_gn.py: batch 4 x 32 groups loses 3-5 us per site, batch 8 wins 2-5 us)
     if ((int64_t)B * groups < 256) return 0;
-    return conv_plan_ksplit(dtype, M, Cin, Cout, workspace_bytes) > 1 &&
+    return conv_plan_ksplit(plan_config(), dtype, M, Cin, Cout, workspace_bytes) > 1 &&
            gmd_gn_from_slabs_ok(split ? GMD_F32 : dtype, B, (int64_t)Hout * Wout, Cout, groups) ? 1 : 0;
 }
 

@@ -2,64 +2,19 @@
 // float32 on the matrix cores as three float16 products): parameter block, operand addressing, LDS image, activation.
 #pragma once
 #include "gmd_common.h"
+#include "gemm_params.h"
+#include "gemm_plan.h"
 #include <mutex>
 
+using namespace gmd;  // GemmParams, Plan and the planner (gemm_params.h, gemm_plan.h)
+
+// gemm_split.hip: float32 on the matrix cores as three float16 products (GMD_F32S / GMD_F32SW / GMD_F32SA), called by gmd_gemm_nt /
+// gmd_gemm_qkv_vt / gmd_conv3x3 of gemm.hip, which validate the parameter block
+// presplit: 0 = both operands plain float32 (GMD_F32S), 1 = W pre-split (GMD_F32SW), 2 = A and W pre-split (GMD_F32SA)
+int gmd_launch_split_gemm(const GemmParams& p, int presplit, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
+int gmd_launch_split_conv(const GemmParams& p, int presplit, void* ws, int64_t ws_bytes, hipStream_t s, const char* name);
+
 namespace {
-
-struct GemmParams {
-    const void* A;
-    const void* W;
-    void* C;
-    int M, N, K;
-    int64_t lda, ldw, ldc, sA, sW, sC;
-    const float* bias;
-    const float* rowbias;
-    int rows_per_group;
-    int64_t ldrb;        // row stride of rowbias (>= N)
-    const void* residual;
-    int64_t ldr, sR;
-    float alpha;
-    int act;
-    int out_f32;
-    int c_split;       // float32 split path: store the output pre-split ([hi | lo] per 32 elements, GMD_F32SA as out_dtype; full-tile row epilogues)
-    unsigned a_bytes, w_bytes;  // extents of the A / W operands (one batch slab) for the buffer descriptors
-    int ksplit;          // > 1: grid z splits K; raw fp32 partial sums go to `ws` [ksplit][M][N], epilogue in splitk_reduce
-    float* ws;
-    // conv3x3 geometry (CONV instantiations only)
-    int Hin, Win, Cin, Hout, Wout, stride, upsample, pad_lo;
-    // conv3x3 K order of the ring kernel: channels are walked in blocks of `cblk` (a multiple of 64 dividing Cin), all nine
-    // taps of a block before the next block.  cblk == Cin is the plain tap-major order.  A smaller block keeps the rows an
-    // XCD re-reads for the next tap inside its 4 MiB L2 (see gmd_conv3x3).
-    int cblk;
-    // optional column statistics of the stored (rounded) output, for a following GroupNorm: {sum, sum of squares} over each
-    // 64-row block and each bucket of `cs_bucket` adjacent columns -> colstats[M/64][N/cs_bucket][2] (ring kernel, row epilogue)
-    float* colstats;
-    int cs_bucket;
-    // split-K only: leave the partial slabs in `ws` and do NOT launch the reduction (the consumer sums them:
-    // gmd_conv3x3_groupnorm -> gn_slab_kernel of norm.hip)
-    int defer_reduce;
-    // tile order of the round-4 kernels inside an XCD's contiguous run of tiles: M-panels are walked in groups of `tile_group`
-    // (m fastest inside a group, then the next N tile, then the next group); 1 = n fastest (the ring kernels' order).  Chosen on
-    // the host so that what an XCD re-reads between reuses stays inside its 4 MiB L2 (gemm.hip: pick_tile_group).
-    int tile_group;
-    // fused Q|K|V projection (gmd_gemm_qkv_vt): column tiles from vt_col0 on are the V columns and leave TRANSPOSED, as the
-    // attention kernels read them: vt_out[sample][column - vt_col0][token], row stride vt_ld, `vt_tokens` rows of C per sample
-    void* vt_out;
-    int vt_col0, vt_tokens;
-    int64_t vt_ld;
-    // in-kernel split-K reduction (round 5, splitk_fixup in gemm.hip): the K slices 0 .. ksplit-2 of a tile leave their accumulator
-    // fragments in `ws` and count themselves in fix_cnt[tile]; the LAST slice (dispatched last) waits for them, adds them in slice
-    // order and runs the fused epilogue -- no slab round trip, no reduction launch.  fix_bytes: extent of the fragment area.
-    int fixup;
-    unsigned fix_bytes;
-    unsigned* fix_cnt;
-};
-
-// The last GMD_WS_TAIL bytes of a caller's workspace hold the arrival counters of the in-kernel split-K reduction (one per tile):
-// zero when the workspace is first handed to the library, left zero by every launch.  Slabs / fragments never reach into them.
-constexpr int kFixupCounters = 16384;
-constexpr int64_t kWsTail = (int64_t)kFixupCounters * 4;
-static inline int64_t gmd_ws_usable_bytes(int64_t bytes) { return bytes > kWsTail ? bytes - kWsTail : 0; }
 
 // (row tile, column tile) of linear tile index L under GemmParams::tile_group
 __device__ __forceinline__ void grouped_tile(int L, int tiles_m, int tiles_n, int group, int& mt, int& nt) {
@@ -195,8 +150,6 @@ __device__ __forceinline__ void colstats_store(float* strip, int lane, const flo
     }
     if (lane < nb) *reinterpret_cast<float2*>(out + lane * 2) = make_float2(s_, q_);
 }
-
-constexpr int BK = 64;  // bf16 elements per K step = 128 bytes = 8 chunks of 16 bytes
 
 // byte offset of 16-byte chunk `chunk` of row `row` in a [rows][128 B] tile; the XOR makes both the
 // 8-lane ds_write_b128 groups and the 16-lane ds_read_b128 groups of a 16x16x32 fragment conflict-free

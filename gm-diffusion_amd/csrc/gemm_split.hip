@@ -25,8 +25,6 @@
 
 namespace {
 
-constexpr int BKS = 32;  // float32 elements per K step = 128 bytes
-
 __device__ __forceinline__ void split2(float a, float b, unsigned& hi, unsigned& lo) { gmd_split2(a, b, hi, lo); }  // gmd_common.h
 __device__ __forceinline__ void split8(const float4& x0, const float4& x1, uint4& hi, uint4& lo) {
     split2(x0.x, x0.y, hi.x, lo.x);
@@ -906,36 +904,6 @@ __global__ __launch_bounds__(256) void split_weights_kernel(const float* __restr
     }
 }
 
-struct SplitPlan {
-    int bm, bn, ksplit;
-};
-}  // namespace
-int gmd_split_colstats_ok(int M, int N, int K, int batch, int64_t ws_bytes, int bucket);
-namespace {
-
-// Tile / split-K selection: the 16-bit heuristic of gemm.hip (make_plan) in units of 64-deep K steps; the tiles are
-// 128 x 160 / 128 x 128 (two workgroups per CU) and 64 x 64 for launches that cannot put 256 large tiles on the chip.
-SplitPlan make_split_plan(int M, int N, int K, int batch, int64_t ws_bytes) {
-    SplitPlan pl{64, 64, 1};
-    if (M >= 96 && N >= 96) {
-        pl.bm = 128;
-        pl.bn = (N % 160 == 0) ? 160 : 128;
-    }
-    const int64_t tiles = (int64_t)((M + pl.bm - 1) / pl.bm) * ((N + pl.bn - 1) / pl.bn) * batch;
-    const int nk = K / 64;
-    if (batch == 1 && tiles < 160 && nk >= 24) {
-        int ks = (int)(((tiles >= 64 ? 512 : 256) + tiles / 2) / tiles);
-        if (ks > nk / 8) ks = nk / 8;
-        if (ks > 16) ks = 16;
-        if (ks > 1 && (int64_t)ks * M * N * (int64_t)sizeof(float) <= ws_bytes) pl.ksplit = ks;
-    }
-    if (batch == 1 && pl.bm == 128 && tiles >= 224 && tiles <= 256 && nk >= 160 && 2 * (int64_t)M * N * (int64_t)sizeof(float) <= ws_bytes)
-        pl.ksplit = 2;
-    if (pl.ksplit == 1 && batch > 1 && M <= 640 && pl.bm == 128) { pl.bm = 64; pl.bn = 64; }
-    if (pl.ksplit == 1 && tiles < 256 && pl.bm == 128) { pl.bm = 64; pl.bn = 64; }
-    return pl;
-}
-
 template <bool CONV, bool WSPLIT, int WM, int WN, int TM, int TN, int NST, bool ASPLIT = false>
 hipError_t launch_split(const GemmParams& p, int gz, hipStream_t s) {
     constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
@@ -949,14 +917,6 @@ hipError_t launch_split(const GemmParams& p, int gz, hipStream_t s) {
     return hipGetLastError();
 }
 
-// 0 (default): never; -1: the loader / converter kernel where it fits (GMD_SPLIT_LC=1); 1: wherever it is instantiated
-// (gmd_gemm_plan_override(.., pf = 244, ..); pf = 9: never).  NOT the default: alone on the chip it wins 3-9 % on one-round launches,
-// but in the two-stream float32 pipeline the whole run is 2.3 % SLOWER with it (bench.py tolerance_path 1894 -> 1937 ms per batch,
-// gpurun_out/s2): like the 16-bit loader-wave kernels it owns its CU (144 KB of LDS), and a workgroup of the other stream on the same
-// CU was already hiding what the loader waves hide.  Kept for single-stream users and as the measured answer
-// to "take the operand split out of the float32 main loop".
-int g_split_lc_mode = [] { const char* e = getenv("GMD_SPLIT_LC"); return (e && e[0] == '1') ? -1 : 0; }();
-
 template <bool CONV, int TN>
 hipError_t launch_split_lc(const GemmParams& p, int gz, hipStream_t s) {
     constexpr int BM = 128, BN = 2 * TN * 16;
@@ -968,54 +928,32 @@ hipError_t launch_split_lc(const GemmParams& p, int gz, hipStream_t s) {
     return hipGetLastError();
 }
 
-// the loader / converter kernel runs ONE workgroup per CU: taken when the launch's 128-row tiles come in (nearly) whole rounds of 256
-bool split_lc_fits(const SplitPlan& pl, const GemmParams& p, int batch) {
-    if (g_split_lc_mode == 0 || batch != 1 || pl.bm != 128 || p.K / BKS < 4) return false;
-    if (g_split_lc_mode == 1) return true;
-    // measured (tools/ab_split_lc.py, bit-identical results): +3...+9 % where the launch is ONE round of workgroups (conv 8x32x32
-    // 640->640 208 -> 196 us, 4x64x64 320->320 110 -> 102 us, linear M=8192 N=640 K=2560 101 -> 95 us); launches of several rounds lose
-    // 10-28 % to two co-resident workgroups of the ring kernel, which overlap one tile's epilogue with the next one's prologue
-    const int64_t tiles = (int64_t)((p.M + 127) / 128) * ((p.N + pl.bn - 1) / pl.bn) * (pl.ksplit > 1 ? pl.ksplit : 1);
-    return tiles >= 200 && tiles <= 256;
-}
-
 template <bool CONV, bool WSPLIT, bool ASPLIT = false>
 int launch_split_any(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
     static_assert(!ASPLIT || WSPLIT, "a pre-split activation meets pre-split weights only (GMD_F32SA)");
-    SplitPlan pl = make_split_plan(p.M, p.N, p.K, batch, ws ? ws_bytes : 0);
-    if (p.act == GMD_ACT_GEGLU) {
-        // value / gate tile pairs inside a wave: even TN (128x128 or 64x64 tiles), unsplit K, every tile full, row epilogue
-        if (pl.bn == 160) pl.bn = 128;
-        pl.ksplit = 1;
+    const int64_t usable = ws ? ws_bytes : 0;
+    const Plan pl = f32_plan(p.M, p.N, p.K, batch, usable, p.act == GMD_ACT_GEGLU);
+    // column statistics, transposed V tiles and pre-split output come out of the full-tile row epilogues only, with 16-byte rows
+    const bool rows_ok = (p.ldc & 3) == 0 && (p.residual == nullptr || (p.ldr & 3) == 0) &&
+                         (p.rowbias == nullptr || ((p.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0));
+    if (p.colstats && !(rows_ok && p.act != GMD_ACT_GEGLU && f32_colstats_ok(p.M, p.N, p.K, batch, usable, p.cs_bucket))) {
+        gmd_set_error("%s: this float32 launch cannot emit column statistics (full-tile row epilogue of an unsplit 128-row launch: ask "
+                      "gmd_gemm_colstats_plan first)", name);
+        return GMD_ERR_UNSUPPORTED;
     }
-    if (p.colstats) {
-        const bool rows_ok = p.act != GMD_ACT_GEGLU && (p.ldc & 3) == 0 && (p.residual == nullptr || (p.ldr & 3) == 0) &&
-                             (p.rowbias == nullptr || ((p.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0));
-        if (!rows_ok || !gmd_split_colstats_ok(p.M, p.N, p.K, batch, ws ? ws_bytes : 0, p.cs_bucket)) {
-            gmd_set_error("%s: this float32 launch cannot emit column statistics (full-tile row epilogue of an unsplit 128-row launch: ask "
-                          "gmd_gemm_colstats_plan first)", name);
-            return GMD_ERR_UNSUPPORTED;
-        }
-    }
-    if (p.vt_out && !(pl.bm == 128 && pl.ksplit == 1 && batch == 1 && p.M % 128 == 0 && p.N % pl.bn == 0 && p.vt_col0 % pl.bn == 0 &&
-                      p.vt_tokens % 64 == 0 && (p.ldc & 3) == 0)) {
+    if (p.vt_out && !(f32_full_rows(pl, p.M, p.N, batch) && p.vt_col0 % pl.bn == 0 && p.vt_tokens % 64 == 0 && (p.ldc & 3) == 0)) {
         gmd_set_error("%s: this float32 launch cannot write transposed V tiles (ask gmd_gemm_qkv_vt_ok first)", name);
         return GMD_ERR_UNSUPPORTED;
     }
-    if (p.c_split) {  // pre-split output: only the full-tile row epilogues write it (gmd_split_out_ok + their alignment conditions)
-        const bool rows_ok = pl.bm == 128 && pl.ksplit == 1 && batch == 1 && p.M % 128 == 0 && p.N % pl.bn == 0 && (p.ldc & 3) == 0 &&
-                             (p.residual == nullptr || (p.ldr & 3) == 0) &&
-                             (p.rowbias == nullptr || ((p.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(p.rowbias) & 15) == 0));
-        if (!rows_ok) {
-            gmd_set_error("%s: this float32 launch cannot store its output pre-split (ask gmd_gemm_out_split_ok first)", name);
-            return GMD_ERR_UNSUPPORTED;
-        }
+    if (p.c_split && !(rows_ok && f32_full_rows(pl, p.M, p.N, batch))) {
+        gmd_set_error("%s: this float32 launch cannot store its output pre-split (ask gmd_gemm_out_split_ok first)", name);
+        return GMD_ERR_UNSUPPORTED;
     }
     p.ksplit = pl.ksplit;
     p.ws = (float*)ws;
     const int gz = pl.ksplit > 1 ? pl.ksplit : batch;
     hipError_t e;
-    if (WSPLIT && !ASPLIT && split_lc_fits(pl, p, batch)) e = pl.bn == 160 ? launch_split_lc<CONV, 5>(p, gz, s) : launch_split_lc<CONV, 4>(p, gz, s);
+    if (WSPLIT && !ASPLIT && split_lc_fits(plan_config(), pl, p.M, p.N, p.K, batch)) e = pl.bn == 160 ? launch_split_lc<CONV, 5>(p, gz, s) : launch_split_lc<CONV, 4>(p, gz, s);
     else if (pl.bm == 128 && pl.bn == 160) e = launch_split<CONV, WSPLIT, 2, 2, 4, 5, 2, ASPLIT>(p, gz, s);
     else if (pl.bm == 128) e = launch_split<CONV, WSPLIT, 2, 2, 4, 4, 2, ASPLIT>(p, gz, s);
     else e = launch_split<CONV, WSPLIT, 2, 2, 2, 2, 2, ASPLIT>(p, gz, s);
@@ -1033,62 +971,14 @@ int launch_split_any(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStr
     return GMD_OK;
 }
 
-// channel block of the conv3x3 K order (conv_channel_block of gemm.hip with 4-byte elements and 32-channel steps)
-int split_channel_block(int B, int Hin, int Win, int Cin, int Cout) {
-    const int64_t rows_total = (int64_t)B * Hin * Win;
-    const int tiles_n = (Cout + 159) / 160;
-    const int64_t rows_resident = (int64_t)(64 / tiles_n > 0 ? 64 / tiles_n : 1) * 128;
-    const int64_t rows = rows_total / 8 < rows_resident ? (rows_total + 7) / 8 : rows_resident;
-    const int64_t budget = 3ll << 20;
-    if (rows * Cin * 4 <= budget) return Cin;
-    int best = 32;
-    for (int d = 32; d < Cin; d += 32)
-        if (Cin % d == 0 && rows * d * 4 <= budget) best = d;
-    return best;
-}
-
 }  // namespace
 
-// producer column statistics (GemmParams::colstats) come out of the full-tile row epilogue of an unsplit launch of the 128-row
-// kernels, whose waves own 64 rows x (BN/2) columns -- a whole number of buckets: the float32 twin of colstats_plan_ok (gemm.hip)
-int gmd_split_colstats_ok(int M, int N, int K, int batch, int64_t ws_bytes, int bucket) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || batch != 1 || bucket <= 0) return 0;
-    const SplitPlan pl = make_split_plan(M, N, K, batch, ws_bytes);
-    return (pl.bm == 128 && pl.ksplit == 1 && M % 128 == 0 && N % pl.bn == 0 && (pl.bn / 2) % bucket == 0) ? 1 : 0;
-}
-
-// the launch can store its result pre-split (GemmParams::c_split): an unsplit launch of full 128-row tiles, whose row epilogues write
-// whole 4-element pieces of 32-element chunks (wave tiles start at multiples of 16 columns; GEGLU: of 8 output columns -- 64 / 80 wide)
-int gmd_split_out_ok(int M, int N, int K, int geglu, int64_t ws_bytes) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32) return 0;
-    SplitPlan pl = make_split_plan(M, N, K, 1, ws_bytes);
-    if (geglu) { if (pl.bn == 160) pl.bn = 128; pl.ksplit = 1; }
-    return (pl.bm == 128 && pl.ksplit == 1 && M % 128 == 0 && N % pl.bn == 0) ? 1 : 0;
-}
-
-// fused Q|K|V projection with transposed V tiles on the float32 matrix-core path (GemmParams::vt_out)
-int gmd_split_qkv_vt_ok(int M, int N, int K, int vt_col0, int vt_tokens, int64_t ws_bytes) {
-    if (M <= 0 || N <= 0 || K <= 0 || K % 32 || vt_col0 <= 0 || vt_col0 >= N || vt_tokens <= 0 || vt_tokens % 64 || M % vt_tokens) return 0;
-    const SplitPlan pl = make_split_plan(M, N, K, 1, ws_bytes);
-    return (pl.bm == 128 && pl.ksplit == 1 && M % 128 == 0 && N % pl.bn == 0 && vt_col0 % pl.bn == 0) ? 1 : 0;
-}
-
-// split-K factor launch_split_any will choose (no GEGLU): gmd_conv3x3_groupnorm / gmd_conv3x3_gn_fusable of gemm.hip
-// (ws_bytes: the USABLE bytes; the C ABI's gmd_split_plan_ksplit of gemm.hip takes the whole workspace)
-int gmd_split_plan_ksplit_usable(int M, int N, int K, int64_t ws_bytes) { return make_split_plan(M, N, K, 1, ws_bytes).ksplit; }
-
-void gmd_split_set_lc(int mode) { g_split_lc_mode = mode; }
-
-// called by gmd_gemm_nt / gmd_conv3x3 (gemm.hip) for the two split dtype codes; the parameter block is validated there
-// presplit: 0 = both operands plain float32 (GMD_F32S), 1 = W pre-split (GMD_F32SW), 2 = A and W pre-split (GMD_F32SA)
-int gmd_launch_split_gemm(const void* params, int presplit, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
-    const GemmParams& p = *reinterpret_cast<const GemmParams*>(params);
+// called by gmd_gemm_nt / gmd_gemm_qkv_vt / gmd_conv3x3 (gemm.hip), which validate the parameter block (gemm_shared.h)
+int gmd_launch_split_gemm(const GemmParams& p, int presplit, int batch, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
     if (presplit == 2) return launch_split_any<false, true, true>(p, batch, ws, ws_bytes, s, name);
     return presplit ? launch_split_any<false, true>(p, batch, ws, ws_bytes, s, name) : launch_split_any<false, false>(p, batch, ws, ws_bytes, s, name);
 }
-int gmd_launch_split_conv(const void* params, int presplit, int B, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
-    GemmParams p = *reinterpret_cast<const GemmParams*>(params);
-    p.cblk = split_channel_block(B, p.Hin, p.Win, p.Cin, p.N);
+int gmd_launch_split_conv(const GemmParams& p, int presplit, void* ws, int64_t ws_bytes, hipStream_t s, const char* name) {
     if (presplit == 2) return launch_split_any<true, true, true>(p, 1, ws, ws_bytes, s, name);
     return presplit ? launch_split_any<true, true>(p, 1, ws, ws_bytes, s, name) : launch_split_any<true, false>(p, 1, ws, ws_bytes, s, name);
 }

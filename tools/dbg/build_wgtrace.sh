@@ -15,6 +15,6 @@ for f in hdr_tail latent_step norm elementwise gemm gemm_split ff_fused attentio
   if [ ${#pids[@]} -ge 4 ]; then wait ${pids[0]}; pids=("${pids[@]:1}"); fi
 done
 wait
-make build/gmd_error.o build/rgbe_rle.o >/dev/null
-/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../tools/dbg/$OUT $BD/*.o build/gmd_error.o build/rgbe_rle.o
+make build/gmd_error.o build/rgbe_rle.o build/gemm_plan.o >/dev/null
+/opt/rocm/bin/hipcc -shared -fPIC --offload-arch=gfx950 -o ../../tools/dbg/$OUT $BD/*.o build/gmd_error.o build/rgbe_rle.o build/gemm_plan.o
 echo built tools/dbg/$OUT
