@@ -39,6 +39,7 @@ SIGNATURES = {
     "gmd_rgbe_rle_encode": [P, I, I, P, L, P],
     "gmd_latent_step": [P, P, P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, P, P, P, P],
     "gmd_dpm_step": [P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, F, F, F, P, P, P, P],
+    "gmd_dpm_sde_step": [P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, F, F, F, F, P, P, P, P],
     "gmd_ddpm_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, F, F, F, F, F, P, P, P],
     "gmd_ddim_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, I, F, F, F, F, F, P, P, P, P],
     "gmd_cfg_std_ratio": [P, I, L, F, P, P],

@@ -482,11 +482,15 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
     """DPM-Solver++ multistep scheduler: the one the reference swaps in for the dual-UNet text->HDR runs
     (``DPMSolverMultistepScheduler.from_config(pipeline.scheduler.config)``,
     scripts/inference/experiments/formal_improved.py:195; scripts/stage2/experiments/scheduler_tuning.py:190-201).
-    Implements diffusers' ``dpmsolver++`` / ``midpoint`` / epsilon-prediction path with ``solver_order`` 1-2,
-    ``lower_order_final`` and ``final_sigmas_type`` zero / sigma_min; Karras / exponential / beta sigma schedules,
-    SDE variants and thresholding raise NotImplementedError.  A host-side state machine over the scheduler protocol:
-    ``step`` / ``fused_step`` run as ONE HIP kernel (gmd_dpm_step) for float32 device tensors, as the same torch
-    expressions on the host otherwise."""
+    Implements diffusers' ``dpmsolver++`` and ``sde-dpmsolver++`` ("DPM++ 2M SDE") algorithms with the ``midpoint`` and ``heun``
+    solver types on the epsilon-prediction path, ``solver_order`` 1-2, ``lower_order_final``, ``euler_at_final`` and
+    ``final_sigmas_type`` zero / sigma_min; Karras / exponential / beta sigma schedules, the non-``++`` algorithms, order 3 and
+    thresholding raise NotImplementedError.  The reference's runs pass ``eta=0.7  # Controls stochasticity`` to the pipeline
+    (formal_improved.py:267), which this solver has no argument for: ``algorithm_type="sde-dpmsolver++"`` is the stochastic
+    sampling that comment intends.  The SDE algorithm draws noise once per step, the last included, after the x0 prediction.
+    A host-side state machine over the scheduler protocol: ``step`` / ``fused_step`` run as ONE HIP kernel (gmd_dpm_step, or
+    gmd_dpm_sde_step for the SDE algorithm) for float32 device tensors, as the same torch expressions on the host otherwise
+    (SURVEY.md §8f-2)."""
 
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
                      solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
@@ -501,10 +505,11 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             raise TypeError(f"DPMSolverMultistepScheduler: unexpected arguments {bad}")
         cfg.update(kwargs)
         self.register_to_config(**cfg)
-        if (cfg["algorithm_type"] != "dpmsolver++" or cfg["solver_type"] != "midpoint" or cfg["prediction_type"] != "epsilon"
-                or cfg["thresholding"] or cfg["use_karras_sigmas"] or cfg["use_exponential_sigmas"] or cfg["use_beta_sigmas"]
-                or cfg["euler_at_final"] or cfg["solver_order"] not in (1, 2)):
-            raise NotImplementedError("only dpmsolver++ / midpoint / epsilon, solver_order <= 2, plain sigmas are implemented")
+        if (cfg["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++") or cfg["solver_type"] not in ("midpoint", "heun")
+                or cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["use_karras_sigmas"]
+                or cfg["use_exponential_sigmas"] or cfg["use_beta_sigmas"] or cfg["solver_order"] not in (1, 2)):
+            raise NotImplementedError("only dpmsolver++ / sde-dpmsolver++, midpoint / heun, epsilon, solver_order <= 2, plain sigmas"
+                                      " are implemented")
         self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
         self.alphas = 1.0 - self.betas
         self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
@@ -599,42 +604,106 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             self.lower_order_nums += 1
         self._step_index += 1
 
-    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0):
-        """One HIP kernel pass (gmd_dpm_step): CFG combine (+rescale), pipeline x0, x0 prediction and the multistep update."""
-        first, alpha_s0, sigma_s0, alpha_t, sigma_t, h, r0 = self._plan_step(timestep)
+    def draws_noise(self, timestep):
+        """True when ``step`` at this timestep consumes the generator: iff the algorithm is an SDE one, then at EVERY step (the last
+        included, where the noise coefficient may be 0)."""
+        return self.config.algorithm_type == "sde-dpmsolver++"
+
+    def _update_coefs(self, first, alpha_t, sigma_t, sigma_s0, h):
+        """(c_x, c_m, c_h, c_n) of ``x_prev = c_x x + c_m D0 + c_h D1 + c_n noise`` (SDE) or ``c_x x - c_m D0 - c_h D1`` (deterministic;
+        c_n None) as float32 0-d tensors, each evaluated left to right as diffusers writes it.  c_h is None at first order.  The
+        deterministic heun term is ``+ k D1``: its c_h is ``-k``, and ``a - (-k) d`` is the same float32 value as ``a + k d``."""
+        c = self.config
+        heun = c.solver_type == "heun"
+        if c.algorithm_type == "sde-dpmsolver++":
+            c_x = sigma_t / sigma_s0 * torch.exp(-h)
+            c_m = alpha_t * (1 - torch.exp(-2.0 * h))
+            c_n = sigma_t * torch.sqrt(1.0 - torch.exp(-2.0 * h))
+            c_h = None if first else (alpha_t * ((1.0 - torch.exp(-2.0 * h)) / (-2.0 * h) + 1.0) if heun else 0.5 * c_m)
+            return c_x, c_m, c_h, c_n
         c_x = sigma_t / sigma_s0
         c_m = alpha_t * (torch.exp(-h) - 1.0)
-        c_h = 0.5 * c_m
+        c_h = None if first else (-(alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)) if heun else 0.5 * c_m)
+        return c_x, c_m, c_h, None
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator=None, noise=None):
+        """One HIP kernel pass (gmd_dpm_step; gmd_dpm_sde_step for the SDE algorithm): CFG combine (+rescale), pipeline x0, x0
+        prediction and the multistep update.  The SDE noise is drawn HERE with ``randn_tensor`` exactly where ``step`` draws it, so
+        a generator shared by the two schedulers of the dual pipeline is consumed in the reference's order."""
+        first, alpha_s0, sigma_s0, alpha_t, sigma_t, h, r0 = self._plan_step(timestep)
+        c_x, c_m, c_h, c_n = self._update_coefs(first, alpha_t, sigma_t, sigma_s0, h)
+        if c_h is None:
+            c_h = torch.tensor(0.0)
         inv_r0 = (1.0 / r0) if r0 is not None else torch.tensor(0.0)
         a = self.alphas_cumprod[int(timestep)]  # the pipeline's own x0 (dual_unet.py:1072) uses the loop timestep
+        if c_n is not None and noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order)
+            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
         ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
         m1 = None if first else self.model_outputs[-1]
-        m0, prev, x0 = ops.dpm_step(eps_in.contiguous(), sample.contiguous(), 1 if first else 2,
-                                    (sigma_s0.item(), alpha_s0.item(), c_x.item(), c_m.item(), c_h.item(), inv_r0.item(),
-                                     a.sqrt().item(), (1 - a).sqrt().item()),
-                                    do_cfg, guidance_scale, m1=m1, ratio=ratio, guidance_rescale=guidance_rescale, want_x0=want_x0)
+        if c_n is None:
+            m0, prev, x0 = ops.dpm_step(eps_in.contiguous(), sample.contiguous(), 1 if first else 2,
+                                        (sigma_s0.item(), alpha_s0.item(), c_x.item(), c_m.item(), c_h.item(), inv_r0.item(),
+                                         a.sqrt().item(), (1 - a).sqrt().item()),
+                                        do_cfg, guidance_scale, m1=m1, ratio=ratio, guidance_rescale=guidance_rescale, want_x0=want_x0)
+        else:
+            m0, prev, x0 = ops.dpm_sde_step(eps_in.contiguous(), sample.contiguous(), 1 if first else 2,
+                                            (sigma_s0.item(), alpha_s0.item(), c_x.item(), c_m.item(), c_h.item(), inv_r0.item(),
+                                             c_n.item(), a.sqrt().item(), (1 - a).sqrt().item()),
+                                            do_cfg, guidance_scale, noise.contiguous(), m1=m1, ratio=ratio,
+                                            guidance_rescale=guidance_rescale, want_x0=want_x0)
         self._advance(m0)
         return prev, x0
 
-    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None):
-        """Same contract as ``PNDMScheduler.fused_step`` (device tensors only; ``generator`` is accepted because ``step`` has
-        the parameter, and unused: this solver is deterministic).  Returns (prev_sample, x0 | None)."""
-        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0)
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None):
+        """Same contract as ``DDPMScheduler.fused_step`` (device float32 tensors only).  ``generator`` and ``noise`` (this step's
+        noise already drawn from ``generator`` by the caller) are used by the SDE algorithm only: the deterministic one never
+        draws.  Returns (prev_sample, x0 | None)."""
+        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise)
 
-    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True):
+    def step(self, model_output, timestep, sample, generator=None, variance_noise=None, return_dict=True, noise=None):
+        """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor.  Either replaces the draw of the SDE
+        algorithm, and the generator is then not touched; the deterministic algorithm ignores all three."""
+        if variance_noise is None:
+            variance_noise = noise
         if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
-            prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False)
+            prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, variance_noise)
             return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+        prev = self._host_step(model_output, timestep, sample, generator, variance_noise)
+        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+    def _host_step(self, model_output, timestep, sample, generator=None, variance_noise=None):
+        """The torch expressions of diffusers' ``DPMSolverMultistepScheduler.step`` (host tensors and 16-bit device tensors; also the
+        reference for the kernel tests).  Returns prev_sample."""
         first, alpha_s0, sigma_s0, alpha_t, sigma_t, h, r0 = self._plan_step(timestep)
         x0_pred = (sample - sigma_s0 * model_output) / alpha_s0  # convert_model_output: dpmsolver++, epsilon
         m1 = self.model_outputs[-1]
+        c = self.config
+        sde, heun = c.algorithm_type == "sde-dpmsolver++", c.solver_type == "heun"
+        if sde and variance_noise is None:
+            variance_noise = randn_tensor(model_output.shape, generator=generator, device=model_output.device, dtype=torch.float32)
         sample = sample.to(torch.float32)
-        if first:
+        D0 = x0_pred
+        D1 = None if first else (1.0 / r0) * (x0_pred - m1)
+        if sde:
+            noise = variance_noise.to(torch.float32)
+            if first:
+                prev = ((sigma_t / sigma_s0 * torch.exp(-h)) * sample + (alpha_t * (1 - torch.exp(-2.0 * h))) * D0
+                        + (sigma_t * torch.sqrt(1.0 - torch.exp(-2.0 * h))) * noise)
+            elif heun:
+                prev = ((sigma_t / sigma_s0 * torch.exp(-h)) * sample + (alpha_t * (1 - torch.exp(-2.0 * h))) * D0
+                        + (alpha_t * ((1.0 - torch.exp(-2.0 * h)) / (-2.0 * h) + 1.0)) * D1
+                        + (sigma_t * torch.sqrt(1.0 - torch.exp(-2.0 * h))) * noise)
+            else:
+                prev = ((sigma_t / sigma_s0 * torch.exp(-h)) * sample + (alpha_t * (1 - torch.exp(-2.0 * h))) * D0
+                        + 0.5 * (alpha_t * (1 - torch.exp(-2.0 * h))) * D1
+                        + (sigma_t * torch.sqrt(1.0 - torch.exp(-2.0 * h))) * noise)
+        elif first:
             prev = (sigma_t / sigma_s0) * sample - (alpha_t * (torch.exp(-h) - 1.0)) * x0_pred
+        elif heun:
+            prev = ((sigma_t / sigma_s0) * sample - (alpha_t * (torch.exp(-h) - 1.0)) * D0
+                    + (alpha_t * ((torch.exp(-h) - 1.0) / h + 1.0)) * D1)
         else:
-            D0, D1 = x0_pred, (1.0 / r0) * (x0_pred - m1)
             prev = ((sigma_t / sigma_s0) * sample - (alpha_t * (torch.exp(-h) - 1.0)) * D0
                     - 0.5 * (alpha_t * (torch.exp(-h) - 1.0)) * D1)
         self._advance(x0_pred)
-        prev = prev.to(model_output.dtype)
-        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+        return prev.to(model_output.dtype)

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "ddpm_step", "ddim_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -1021,6 +1021,25 @@ def dpm_step(eps_in, x, order, coefs, do_cfg, guidance_scale, m1=None, ratio=Non
     c = [float(v) for v in coefs]
     check(lib().gmd_dpm_step(_ptr(eps_in), _ptr(x), _ptr(m1), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
                              float(guidance_rescale), int(order), *c, _ptr(m0), _ptr(x_prev), _ptr(x0), _stream()), "gmd_dpm_step")
+    return m0, x_prev, x0
+
+
+def dpm_sde_step(eps_in, x, order, coefs, do_cfg, guidance_scale, noise, m1=None, ratio=None, guidance_rescale=0.0, want_x0=False):
+    """Fused CFG + x0 + SDE-DPM-Solver++ (orders 1-2) update.  coefs = (sigma_s0, alpha_s0, c_x, c_m, c_h, inv_r0, c_n, sqrt_alpha,
+    sqrt_one_minus_alpha); ``noise`` is required and added at every step (also with c_n == 0).  Returns (m0, x_prev, x0|None)."""
+    _dev(eps_in, x, m1, noise, ratio)
+    for t in (eps_in, x, m1, noise):
+        _f32(t, "latent tensors")
+    if noise is None or noise.shape != x.shape:
+        raise HipExtensionError("dpm_sde_step: noise must have the sample's shape")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    m0 = torch.empty_like(x)
+    x_prev = torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    c = [float(v) for v in coefs]
+    check(lib().gmd_dpm_sde_step(_ptr(eps_in), _ptr(x), _ptr(m1), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
+                                 float(guidance_rescale), int(order), *c, _ptr(m0), _ptr(x_prev), _ptr(x0), _stream()), "gmd_dpm_sde_step")
     return m0, x_prev, x0
 
 

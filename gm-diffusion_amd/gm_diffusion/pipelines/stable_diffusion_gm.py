@@ -359,12 +359,15 @@ class _GMPipelineBase(DiffusionPipeline):
         or None when there is nothing to pre-draw (deterministic scheduler, device generator, global RNG) or when the noise
         of all steps would exceed PREDRAW_NOISE_BYTES (DDPM's default 1000 steps at 1024x1024, batch 8, two schedulers is
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
-        DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.
+        DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.  So does a
+        ``DPMSolverMultistepScheduler`` with the SDE algorithm; a deterministic one has nothing to pre-draw.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
-        from ..components.schedulers import DDIMScheduler, DDPMScheduler
+        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
 
-        if generator is None or not all(isinstance(s_, (DDPMScheduler, DDIMScheduler)) for s_ in schedulers):
+        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler))
+                                 or (isinstance(s_, DPMSolverMultistepScheduler) and s_.draws_noise(None)))
+        if generator is None or not all(takes_part(s_) for s_ in schedulers):
             return None
         gens = generator if isinstance(generator, list) else [generator]
         if any(g_.device.type != "cpu" for g_ in gens):

@@ -192,6 +192,25 @@ int gmd_dpm_step(const float* eps_in, const float* x, const float* m1, int B, in
                  float sqrt_alpha, float sqrt_one_minus_alpha,
                  float* m0_out, float* x_prev, float* x0, gmd_stream_t stream);
 
+/* SDE-DPM-Solver++ multistep ("DPM++ 2M SDE": algorithm_type "sde-dpmsolver++", midpoint / heun, epsilon, orders 1-2) -- the
+ * stochastic sampling the reference's dual-UNet runs ask for with `eta=0.7  # Controls stochasticity`
+ * (scripts/inference/experiments/formal_improved.py:195, 267), which DPM-Solver has no `eta` for.  Added within ABI v14 (purely
+ * additive: no existing signature changed).  Fused with the same CFG combine / rescale and pipeline x0 as gmd_latent_step, in
+ * the float32 operation order of diffusers' dpm_solver_first_order_update / multistep_dpm_solver_second_order_update:
+ *   m0 = (x - sigma_s0*eps)/alpha_s0;  x_prev = c_x*x + c_m*m0 [ + c_h*(inv_r0*(m0 - m1)) when order == 2 ] + c_n*noise
+ * c_x = sigma_t/sigma_s0*exp(-h), c_m = alpha_t*(1 - exp(-2h)), c_n = sigma_t*sqrt(1 - exp(-2h)), inv_r0 = 1/r0 and
+ * c_h = 0.5*c_m (midpoint) or alpha_t*((1 - exp(-2h))/(-2h) + 1) (heun): float32 scalars computed by the host exactly as
+ * diffusers computes its 0-dim tensors.  The noise is required and added at EVERY step, also with c_n == 0 (the last step of
+ * a final_sigmas_type "zero" schedule); it is drawn by the host scheduler from the caller's generator, in the reference's
+ * order (SDR first, GM second).  m0_out is the x0 prediction the host keeps for the next step; x0 may be NULL.  c_n must be
+ * >= 0 (a NaN is refused).  The deterministic heun solver type needs no entry point of its own: it is gmd_dpm_step with
+ * c_h = -alpha_t*((exp(-h) - 1)/h + 1), since a - (-k)*d and a + k*d are the same float32 value. */
+int gmd_dpm_sde_step(const float* eps_in, const float* x, const float* m1, const float* noise, int B, int64_t chw,
+                     int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                     int order, float sigma_s0, float alpha_s0, float c_x, float c_m, float c_h, float inv_r0, float c_n,
+                     float sqrt_alpha, float sqrt_one_minus_alpha,
+                     float* m0_out, float* x_prev, float* x0, gmd_stream_t stream);
+
 /* DDPM ancestral step -- the scheduler the reference's Stage-3 CLI constructs (scripts/inference/generate_hdr.py:162,
  * used by the pipeline call at :212-218) -- fused with the same CFG combine / rescale and pipeline x0 as gmd_latent_step,
  * in the float32 operation order of diffusers' DDPMScheduler.step:
