@@ -6,6 +6,8 @@
 // expressions of the reference so the results are bit-identical to the CPU path given identical eps.
 #include "gmd_common.h"
 
+#include <cmath>
+
 #pragma clang fp contract(off)
 
 namespace {
@@ -197,6 +199,42 @@ __global__ __launch_bounds__(kThreads) void ddim_step_kernel(
     }
 }
 
+// Euler / Euler-ancestral step (diffusers' EulerDiscreteScheduler / EulerAncestralDiscreteScheduler, epsilon prediction, s_churn == 0)
+// fused with the CFG combine, in the operation order of their torch expressions (float32, no FMA contraction):
+//   p0     = x - sigma_hat * eps            pred_original_sample (also the pipeline's x0: sigma space has no other form)
+//   d      = (x - p0) / sigma_hat           derivative
+//   x_prev = x + d * dt                     dt = sigma_next - sigma_hat (Euler) or sigma_down - sigma (ancestral)
+//   x_prev = x_prev + noise * sigma_up      ancestral only (noise == nullptr otherwise)
+// The add happens whenever a noise tensor is given, also with sigma_up == 0 (the last step, sigma_to == 0): torch adds the zero
+// product there too, and -0.0 + 0.0 is not -0.0.  The noise is drawn by the HOST scheduler, as for DDPM and DDIM.
+__global__ __launch_bounds__(kThreads) void euler_step_kernel(
+    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
+    float gs, const float* __restrict__ ratio, float gr, float sigma_hat, float dt, float sigma_up, float* __restrict__ x_prev,
+    float* __restrict__ pred_x0) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const int64_t n = (int64_t)B * chw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float eps;
+        if (do_cfg) {
+            const float u = eps_in[i], t = eps_in[n + i];
+            eps = u + gs * (t - u);  // dual.py:1065
+            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
+                const float resc = eps * ratio[i / chw];
+                eps = gr * resc + (1.0f - gr) * eps;
+            }
+        } else {
+            eps = eps_in[i];
+        }
+        const float xt = x[i];
+        const float p0 = xt - sigma_hat * eps;
+        if (pred_x0) pred_x0[i] = p0;
+        const float d = (xt - p0) / sigma_hat;
+        float r = xt + d * dt;
+        if (noise) r = r + noise[i] * sigma_up;
+        x_prev[i] = r;
+    }
+}
+
 // one block per sample: unbiased std over chw of text eps and of the guided eps
 __global__ __launch_bounds__(kThreads) void cfg_std_ratio_kernel(const float* __restrict__ eps_in, int B, int64_t chw,
                                                                  float gs, float* __restrict__ ratio) {
@@ -227,9 +265,12 @@ __global__ __launch_bounds__(kThreads) void cfg_std_ratio_kernel(const float* __
     }
 }
 
-template <typename T>
-__global__ __launch_bounds__(kThreads) void pack_kernel(const float* __restrict__ s0, int C0, const float* __restrict__ s1,
-                                                        int C1, int B, int64_t HW, int dup, T* __restrict__ out, int CP) {
+// kScaled: each source is divided by its own float32 divisor before the one rounding to T (a sigma-space scheduler's
+// scale_model_input, sample / ((sigma**2 + 1) ** 0.5): a float32 division, not a reciprocal multiply); padding channels stay zero.
+// The plain instantiation holds no division and ignores div0 / div1.
+template <typename T, bool kScaled>
+__global__ __launch_bounds__(kThreads) void pack_kernel(const float* __restrict__ s0, int C0, float div0, const float* __restrict__ s1,
+                                                        int C1, float div1, int B, int64_t HW, int dup, T* __restrict__ out, int CP) {
     GMD_WG_TRACE_SCOPE(WGK_PACK);
     // one thread per (pixel, 8-channel group) of the padded output
     const int groups = CP / 8;
@@ -243,8 +284,13 @@ __global__ __launch_bounds__(kThreads) void pack_kernel(const float* __restrict_
         for (int j = 0; j < 8; ++j) {
             const int c = g * 8 + j;
             float val = 0.0f;
-            if (c < C0) val = s0[(b * C0 + c) * HW + p];
-            else if (c < C0 + C1) val = s1[(b * C1 + (c - C0)) * HW + p];
+            if (c < C0) {
+                val = s0[(b * C0 + c) * HW + p];
+                if (kScaled) val = val / div0;
+            } else if (c < C0 + C1) {
+                val = s1[(b * C1 + (c - C0)) * HW + p];
+                if (kScaled) val = val / div1;
+            }
             v[j] = val;
         }
         for (int d = 0; d < dup; ++d) {
@@ -375,6 +421,23 @@ int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B
     return GMD_OK;
 }
 
+int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
+                   const float* rescale_ratio, float guidance_rescale, float sigma_hat, float dt, float sigma_up, float* x_prev,
+                   float* pred_x0, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && chw > 0, "gmd_euler_step: bad shape B=%d chw=%lld", B, (long long)chw);
+    // written as (v > 0) / (v >= 0) so that a NaN is refused too
+    GMD_REQUIRE(sigma_hat > 0.0f, "gmd_euler_step: sigma_hat must be > 0 (got %g)", (double)sigma_hat);
+    GMD_REQUIRE(sigma_up >= 0.0f, "gmd_euler_step: sigma_up must be >= 0 (got %g)", (double)sigma_up);
+    GMD_REQUIRE(std::isfinite(dt), "gmd_euler_step: dt must be finite (got %g)", (double)dt);
+    if (B == 0) return GMD_OK;
+    GMD_REQUIRE(eps_in && x && x_prev, "gmd_euler_step: null pointer");
+    euler_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
+        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sigma_hat, dt, sigma_up,
+        x_prev, pred_x0);
+    GMD_CHECK_LAUNCH("gmd_euler_step");
+    return GMD_OK;
+}
+
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale, float* ratio, gmd_stream_t stream) {
     GMD_REQUIRE(B >= 0 && chw >= 2, "gmd_cfg_std_ratio: need at least 2 elements per sample");
     if (B == 0) return GMD_OK;
@@ -396,9 +459,30 @@ int gmd_pack_unet_input(const float* src0, int C0, const float* src1, int C1, in
     GMD_REQUIRE(gmd_known_dtype(out_dtype), "gmd_pack_unet_input: bad dtype %d", out_dtype);
     gmd_for_dtype(out_dtype, [&](auto tag) {
         using T = decltype(tag);
-        pack_kernel<T><<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(src0, C0, src1, C1, B, HW, dup, (T*)out, CP);
+        pack_kernel<T, false><<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(src0, C0, 1.0f, src1, C1, 1.0f, B, HW, dup, (T*)out, CP);
     });
     GMD_CHECK_LAUNCH("gmd_pack_unet_input");
+    return GMD_OK;
+}
+
+int gmd_pack_unet_input_scaled(const float* src0, int C0, float div0, const float* src1, int C1, float div1, int B, int64_t HW, int dup,
+                               void* out, int CP, int out_dtype, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && HW >= 0 && C0 > 0 && C1 >= 0, "gmd_pack_unet_input_scaled: bad shape");
+    GMD_REQUIRE(CP % 8 == 0 && CP >= C0 + C1, "gmd_pack_unet_input_scaled: CP=%d must be a multiple of 8 and >= %d", CP, C0 + C1);
+    GMD_REQUIRE(dup == 1 || dup == 2, "gmd_pack_unet_input_scaled: dup must be 1 or 2");
+    GMD_REQUIRE(C1 == 0 || src1, "gmd_pack_unet_input_scaled: src1 is null");
+    // written as (v > 0) so that a NaN is refused too
+    GMD_REQUIRE(div0 > 0.0f, "gmd_pack_unet_input_scaled: div0 must be > 0 (got %g)", (double)div0);
+    GMD_REQUIRE(C1 == 0 || div1 > 0.0f, "gmd_pack_unet_input_scaled: div1 must be > 0 (got %g)", (double)div1);
+    if ((int64_t)B * HW == 0) return GMD_OK;
+    GMD_REQUIRE(src0 && out, "gmd_pack_unet_input_scaled: null pointer");
+    const int64_t total = (int64_t)B * HW * (CP / 8);
+    GMD_REQUIRE(gmd_known_dtype(out_dtype), "gmd_pack_unet_input_scaled: bad dtype %d", out_dtype);
+    gmd_for_dtype(out_dtype, [&](auto tag) {
+        using T = decltype(tag);
+        pack_kernel<T, true><<<grid_for(total), kThreads, 0, (hipStream_t)stream>>>(src0, C0, div0, src1, C1, div1, B, HW, dup, (T*)out, CP);
+    });
+    GMD_CHECK_LAUNCH("gmd_pack_unet_input_scaled");
     return GMD_OK;
 }
 

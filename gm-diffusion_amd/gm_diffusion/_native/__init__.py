@@ -42,8 +42,10 @@ SIGNATURES = {
     "gmd_dpm_sde_step": [P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, F, F, F, F, P, P, P, P],
     "gmd_ddpm_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, F, F, F, F, F, P, P, P],
     "gmd_ddim_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, I, F, F, F, F, F, P, P, P, P],
+    "gmd_euler_step": [P, P, P, I, L, I, F, P, F, F, F, F, P, P, P],
     "gmd_cfg_std_ratio": [P, I, L, F, P, P],
     "gmd_pack_unet_input": [P, I, P, I, I, L, I, P, I, I, P],
+    "gmd_pack_unet_input_scaled": [P, I, F, P, I, F, I, L, I, P, I, I, P],
     "gmd_unpack_nchw": [P, I, L, I, I, L, P, P],
     "gmd_gemm_plan_override": [I, I, I, I],
     "gmd_gemm_plan_family": [I],

@@ -1,8 +1,9 @@
 """
 Schedulers for the MI355X build: ``PNDMScheduler`` (PLMS, the "50 PNDM steps" configuration of
 scripts/stage2/train_gm_unet.py:171-176), ``DDPMScheduler`` (scripts/inference/generate_hdr.py:162),
-``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188) and
-``DPMSolverMultistepScheduler``.  In the reference they come from ``diffusers``; these
+``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188),
+``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` (the only ones
+whose ``init_noise_sigma`` and ``scale_model_input`` do something).  In the reference they come from ``diffusers``; these
 classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241, 610-625, 715,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
 access), ``set_timesteps``, ``timesteps``, ``order``, ``init_noise_sigma``,
@@ -707,3 +708,299 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
                     - 0.5 * (alpha_t * (torch.exp(-h) - 1.0)) * D1)
         self._advance(x0_pred)
         return prev.to(model_output.dtype)
+
+
+@dataclass
+class EulerSchedulerOutput(_Output):
+    prev_sample: torch.Tensor
+    pred_original_sample: torch.Tensor = None
+
+
+class _SigmaSchedulerBase(_SchedulerBase):
+    """What the sigma-space (variance-exploding) schedulers share: the sigma / timestep tables of diffusers' ``set_timesteps``
+    (float64 numpy, stored as float32 tensors), ``init_noise_sigma``, ``scale_model_input`` and the step index.  Unlike the
+    variance-preserving schedulers above, the UNet input is ``sample / (sigma**2 + 1) ** 0.5`` and the timesteps are float32,
+    fractional for ``linspace`` spacing and Karras sigmas: a step is selected by ``step_index``, never by an integer timestep."""
+
+    sigma_space = True  # the pipelines' fused loops divide the UNet input by ``input_divisor`` inside the pack kernel
+    _name = "_SigmaSchedulerBase"
+
+    def _init_sigma_space(self, kwargs):
+        cfg = dict(self._defaults)
+        bad = [k for k in kwargs if k not in cfg]
+        if bad:
+            raise TypeError(f"{self._name}: unexpected arguments {bad}")
+        cfg.update(kwargs)
+        self.register_to_config(**cfg)
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"{self._name}: only prediction_type 'epsilon' is implemented (got {cfg['prediction_type']!r})")
+        if cfg.get("interpolation_type", "linear") != "linear":
+            raise NotImplementedError(f"{self._name}: only interpolation_type 'linear' is implemented")
+        if cfg.get("timestep_type", "discrete") != "discrete":
+            raise NotImplementedError(f"{self._name}: only timestep_type 'discrete' is implemented")
+        if cfg.get("final_sigmas_type", "zero") != "zero":
+            raise NotImplementedError(f"{self._name}: only final_sigmas_type 'zero' is implemented")
+        if cfg.get("use_exponential_sigmas", False) or cfg.get("use_beta_sigmas", False):
+            raise NotImplementedError(f"{self._name}: exponential and beta sigmas are not implemented (plain and Karras sigmas are)")
+        if cfg.get("rescale_betas_zero_snr", False):
+            raise NotImplementedError(f"{self._name}: rescale_betas_zero_snr is not implemented")
+        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
+        ts = np.linspace(0, cfg["num_train_timesteps"] - 1, cfg["num_train_timesteps"], dtype=float)[::-1].copy()
+        self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
+        self.sigmas = torch.cat([sigmas, torch.zeros(1)])
+        self._ts_host = self.timesteps.tolist()
+        self.num_inference_steps = None
+        self._step_index = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    @property
+    def init_noise_sigma(self):
+        max_sigma = self.sigmas.max()
+        if self.config.timestep_spacing in ("linspace", "trailing"):
+            return max_sigma
+        return (max_sigma ** 2 + 1) ** 0.5
+
+    def _train_sigmas(self):
+        """((1 - a) / a) ** 0.5 of the float32 table, as float64."""
+        return (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).numpy().astype(np.float64)
+
+    @staticmethod
+    def _sigma_to_t(sigma, log_sigmas):
+        """diffusers' ``_sigma_to_t``: the fractional train timestep whose log-sigma (linear between table entries) is log(sigma)."""
+        log_sigma = np.log(np.maximum(sigma, 1e-10))
+        dists = log_sigma - log_sigmas[:, np.newaxis]
+        low_idx = np.cumsum((dists >= 0), axis=0).argmax(axis=0).clip(max=log_sigmas.shape[0] - 2)
+        high_idx = low_idx + 1
+        low, high = log_sigmas[low_idx], log_sigmas[high_idx]
+        w = np.clip((low - log_sigma) / (low - high), 0, 1)
+        return ((1 - w) * low_idx + w * high_idx).reshape(np.shape(sigma))
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        """diffusers' tables.  ``sigmas``: a custom schedule INCLUDING its terminal value (the last entry, usually 0, gets no
+        timestep); ``timesteps``: custom (possibly fractional) timesteps.  Everything is computed in float64 numpy and stored as
+        float32 (diffusers takes the logarithms of the sigma table in float32; here they are float64 like the rest)."""
+        c = self.config
+        if timesteps is not None and sigmas is not None:
+            raise ValueError("Only one of `timesteps` or `sigmas` should be set.")
+        if num_inference_steps is None and timesteps is None and sigmas is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps` or `sigmas.")
+        if (timesteps is not None or sigmas is not None) and c.get("use_karras_sigmas", False):
+            raise ValueError("Cannot set `timesteps` or `sigmas` with `config.use_karras_sigmas = True`.")
+        train = self._train_sigmas()
+        log_sigmas = np.log(train)
+        T = c.num_train_timesteps
+        if sigmas is not None:
+            sigmas = np.array(sigmas).astype(np.float32)
+            if sigmas.ndim != 1 or len(sigmas) < 2 or not np.all(sigmas[:-1] > 0) or not np.all(np.diff(sigmas) < 0):
+                raise ValueError("custom `sigmas` must be positive and decreasing, followed by their terminal value")
+            ts = self._sigma_to_t(sigmas[:-1].astype(np.float64), log_sigmas)
+        else:
+            if timesteps is not None:
+                ts = np.array(timesteps).astype(np.float32)
+            elif c.timestep_spacing == "linspace":
+                ts = np.linspace(0, T - 1, num_inference_steps, dtype=np.float32)[::-1].copy()
+            elif c.timestep_spacing == "leading":
+                ratio = T // num_inference_steps
+                ts = (np.arange(0, num_inference_steps) * ratio).round()[::-1].copy().astype(np.float32)
+                ts += c.steps_offset
+            elif c.timestep_spacing == "trailing":
+                ratio = T / num_inference_steps
+                ts = (np.arange(T, 0, -ratio)).round().copy().astype(np.float32)
+                ts -= 1
+            else:
+                raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'linspace', 'leading' or 'trailing'.")
+            sig = np.interp(ts, np.arange(0, len(train)), train)
+            if c.get("use_karras_sigmas", False):
+                sig = self._convert_to_karras(sig, len(ts))
+                ts = self._sigma_to_t(sig, log_sigmas)
+            sigmas = np.concatenate([sig, [0.0]]).astype(np.float32)
+        ts32 = ts.astype(np.float32)
+        if len(np.unique(ts32)) != len(ts32):
+            # e.g. custom sigmas above the training range, which all map to the last train timestep: the step could no longer be
+            # told from the timestep, and diffusers' rule for a repeated timestep (take the second) would skip the first sigma
+            raise ValueError(f"{self._name}: the schedule holds a timestep twice ({ts32.tolist()}); every step needs its own timestep"
+                             " (custom sigmas must lie inside the training range)")
+        self.num_inference_steps = len(ts)
+        self.sigmas = torch.from_numpy(sigmas).to(dtype=torch.float32)  # host: the step's scalars are computed from 0-d views of it
+        self.timesteps = torch.from_numpy(ts32).to(device=device)
+        self._ts_host = torch.from_numpy(ts32).tolist()
+        self._step_index = None
+
+    @staticmethod
+    def _convert_to_karras(in_sigmas, num_inference_steps):
+        """Karras et al. (2022) noise levels between the schedule's own ends, rho = 7."""
+        sigma_min, sigma_max = float(in_sigmas[-1]), float(in_sigmas[0])
+        rho = 7.0
+        ramp = np.linspace(0, 1, num_inference_steps)
+        min_inv_rho, max_inv_rho = sigma_min ** (1 / rho), sigma_max ** (1 / rho)
+        return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
+
+    def _init_step_index(self, timestep):
+        """The entry equal to ``timestep`` as a float32 value (``set_timesteps`` refuses a schedule in which one occurs twice)."""
+        t = float(timestep)
+        idx = [k for k, v in enumerate(self._ts_host) if v == t]
+        if not idx:
+            raise ValueError(f"{self._name}: timestep {t!r} is not in the schedule set by `set_timesteps` (timesteps are float32"
+                             " values and may be fractional: pass them on unchanged)")
+        self._step_index = idx[0]
+
+    def _sigma(self, timestep):
+        """The current step's sigma as a float32 0-d tensor (fixes the step index from ``timestep`` on first use)."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            if timestep is None:
+                raise ValueError(f"{self._name}: a timestep is needed until the first call has fixed the step index")
+            self._init_step_index(timestep)
+        return self.sigmas[self._step_index]
+
+    def input_divisor(self, timestep=None):
+        """(sigma**2 + 1) ** 0.5 of the current step as a float: what ``scale_model_input`` divides by, evaluated on a float32 0-d
+        tensor exactly as there.  The fused loops hand it to the UNet's input pack."""
+        sigma = self._sigma(timestep)
+        return float((sigma ** 2 + 1) ** 0.5)
+
+    def scale_model_input(self, sample, timestep=None):
+        sigma = self._sigma(timestep)
+        return sample / ((sigma ** 2 + 1) ** 0.5).to(sample.device)
+
+    def _finish(self, prev, p0, return_dict):
+        self._step_index += 1
+        return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+
+
+class EulerDiscreteScheduler(_SigmaSchedulerBase):
+    """Euler (Karras et al. 2022, algorithm 2 without churn): the scheduler an SDXL-base checkpoint names, in sigma space.
+    Implements diffusers' epsilon-prediction path with the three timestep spacings, plain or Karras sigmas and custom
+    ``sigmas`` / ``timesteps``; v-prediction, ``s_churn`` > 0, log-linear interpolation, continuous timesteps, a non-zero final
+    sigma and exponential / beta sigmas raise NotImplementedError.  It draws no noise.  ``step`` / ``fused_step`` run as ONE HIP
+    kernel (gmd_euler_step) for float32 device tensors, as the same torch expressions (``_host_step``) otherwise; the host computes
+    the step's scalars on float32 0-d tensors exactly as diffusers does."""
+
+    _name = "EulerDiscreteScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", interpolation_type="linear", use_karras_sigmas=False, use_exponential_sigmas=False,
+                     use_beta_sigmas=False, sigma_min=None, sigma_max=None, timestep_spacing="linspace", timestep_type="discrete",
+                     steps_offset=0, rescale_betas_zero_snr=False, final_sigmas_type="zero")
+
+    def __init__(self, **kwargs):
+        self._init_sigma_space(kwargs)
+        if self.config.sigma_min is not None or self.config.sigma_max is not None:
+            raise NotImplementedError("EulerDiscreteScheduler: sigma_min / sigma_max overrides of the Karras range are not implemented")
+
+    def draws_noise(self, timestep):
+        """False: without churn the Euler step never consumes the generator."""
+        return False
+
+    def _coefs(self, timestep, s_churn):
+        if s_churn > 0:
+            raise NotImplementedError("EulerDiscreteScheduler: s_churn > 0 (stochastic churn) is not implemented")
+        sigma = self._sigma(timestep)
+        sigma_hat = sigma * (0.0 + 1)  # gamma == 0
+        return sigma_hat, self.sigmas[self._step_index + 1] - sigma_hat
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, s_churn=0.0):
+        """One HIP kernel pass (gmd_euler_step): CFG combine (+rescale), x0 prediction and the Euler update.
+        Returns (prev_sample, pred_original_sample | None)."""
+        sigma_hat, dt = self._coefs(timestep, s_churn)
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        out = ops.euler_step(eps_in.contiguous(), sample.contiguous(), (sigma_hat.item(), dt.item(), 0.0), do_cfg, guidance_scale,
+                             ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
+        self._step_index += 1
+        return out
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None):
+        """Same contract as ``DDIMScheduler.fused_step`` (device float32 tensors only); ``generator`` and ``noise`` are accepted and
+        unused.  The x0 returned is ``sample - sigma * eps``: in sigma space the pipeline's x0 and pred_original_sample coincide.
+        Returns (prev_sample, x0 | None)."""
+        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0)
+
+    def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
+             return_dict=True, noise=None):
+        """diffusers' signature; ``noise`` (not in diffusers) is what the pipelines pass to every stochastic scheduler: unused here."""
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, s_churn)
+            return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+        return self._host_step(model_output, timestep, sample, s_churn, return_dict)
+
+    def _host_step(self, model_output, timestep, sample, s_churn=0.0, return_dict=True):
+        """The torch expressions of diffusers' ``EulerDiscreteScheduler.step`` (host tensors; also the reference for the kernel test)."""
+        sigma_hat, dt = (c.to(model_output.device) for c in self._coefs(timestep, s_churn))
+        sample = sample.to(torch.float32)
+        p0 = sample - sigma_hat * model_output
+        derivative = (sample - p0) / sigma_hat
+        prev = sample + derivative * dt
+        return self._finish(prev.to(model_output.dtype), p0, return_dict)
+
+
+class EulerAncestralDiscreteScheduler(_SigmaSchedulerBase):
+    """Euler ancestral sampling (k-diffusion's ``sample_euler_ancestral`` as diffusers restates it): an Euler step down to
+    ``sigma_down`` followed by fresh noise of standard deviation ``sigma_up``.  Noise is drawn from the caller's generator at EVERY
+    step, the last included (where sigma_up is 0): n steps take n draws.  Same spacings and limits as ``EulerDiscreteScheduler``;
+    ``use_karras_sigmas`` is accepted here too (diffusers' class has plain sigmas only).  ``step`` / ``fused_step`` run as ONE HIP
+    kernel (gmd_euler_step with a noise tensor) for float32 device tensors, as the torch expressions (``_host_step``) otherwise."""
+
+    _name = "EulerAncestralDiscreteScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     prediction_type="epsilon", use_karras_sigmas=False, timestep_spacing="linspace", steps_offset=0,
+                     rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        self._init_sigma_space(kwargs)
+
+    def draws_noise(self, timestep):
+        """True: ``step`` consumes the generator at every step, the last included."""
+        return True
+
+    def _coefs(self, timestep):
+        """(sigma, dt = sigma_down - sigma, sigma_up) as float32 0-d tensors, evaluated exactly as diffusers evaluates them."""
+        sigma = self._sigma(timestep)
+        sigma_from, sigma_to = self.sigmas[self._step_index], self.sigmas[self._step_index + 1]
+        sigma_up = (sigma_to ** 2 * (sigma_from ** 2 - sigma_to ** 2) / sigma_from ** 2) ** 0.5
+        sigma_down = (sigma_to ** 2 - sigma_up ** 2) ** 0.5
+        return sigma, sigma_down - sigma, sigma_up
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator=None, noise=None):
+        """One HIP kernel pass (gmd_euler_step): CFG combine (+rescale), x0 prediction, the Euler update to sigma_down and the
+        ancestral noise.  The noise is drawn HERE with ``randn_tensor`` exactly where ``step`` draws it, so a generator shared by the
+        two schedulers of the dual pipeline is consumed in call order (SDR first, GM second)."""
+        sigma, dt, sigma_up = self._coefs(timestep)
+        if noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order)
+            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        out = ops.euler_step(eps_in.contiguous(), sample.contiguous(), (sigma.item(), dt.item(), sigma_up.item()), do_cfg, guidance_scale,
+                             noise=noise.contiguous(), ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
+        self._step_index += 1
+        return out
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None):
+        """Same contract as ``DDPMScheduler.fused_step`` (device float32 tensors only).  ``noise``: this step's noise already drawn
+        from ``generator`` by the caller.  Returns (prev_sample, x0 | None) with x0 = ``sample - sigma * eps``."""
+        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise)
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
+        """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor: what ``generator`` would have
+        given at this step, so it may come together with the generator, which is then not touched."""
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, generator, noise)
+            return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+        return self._host_step(model_output, timestep, sample, generator, return_dict, noise)
+
+    def _host_step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
+        """The torch expressions of diffusers' ``EulerAncestralDiscreteScheduler.step`` (host tensors; the kernel test's reference)."""
+        dev = model_output.device
+        sigma, dt, sigma_up = (c.to(dev) for c in self._coefs(timestep))
+        sample = sample.to(torch.float32)
+        p0 = sample - sigma * model_output
+        derivative = (sample - p0) / sigma
+        prev = sample + derivative * dt
+        if noise is None:
+            noise = randn_tensor(model_output.shape, generator=generator, device=dev, dtype=model_output.dtype)
+        prev = prev + noise * sigma_up
+        return self._finish(prev.to(model_output.dtype), p0, return_dict)

@@ -879,9 +879,11 @@ class UNet2DConditionModel(_HipModule):
             ehs = ehs.float()
         return ops.cast(ehs, self._dtype)
 
-    def pack_input(self, sample, dup=1, out=None):
+    def pack_input(self, sample, dup=1, out=None, div=None):
         """sample: float32 NCHW tensor, or a tuple ``(cond, x)`` concatenated on channels (conditioning first:
-        stable_diffusion_gm.py:1045, dual_unet.py:1080); dup=2 duplicates the batch for CFG (gm.py:1047)."""
+        stable_diffusion_gm.py:1045, dual_unet.py:1080); dup=2 duplicates the batch for CFG (gm.py:1047).  ``div``: None, or the
+        float32 divisors ``(d_cond, d_x)`` of the two parts (a single tensor takes a number or ``(d, 1.0)``): a sigma-space
+        scheduler's ``scale_model_input`` folded into the pack (gm.py:1048)."""
         self._ensure()
         a, b = (sample if isinstance(sample, (tuple, list)) else (sample, None))
         if a.dtype != torch.float32:
@@ -891,7 +893,10 @@ class UNet2DConditionModel(_HipModule):
         nch = a.shape[1] + (0 if b is None else b.shape[1])
         if nch != self.config.in_channels:
             raise ValueError(f"UNet expects {self.config.in_channels} input channels, got {nch}")
-        return ops.pack_unet_input(a.contiguous(), None if b is None else b.contiguous(), dup, self._cin_pad, self._dtype, out=out)
+        if div is None:
+            return ops.pack_unet_input(a.contiguous(), None if b is None else b.contiguous(), dup, self._cin_pad, self._dtype, out=out)
+        div = tuple(div) if isinstance(div, (tuple, list)) else (div, 1.0)
+        return ops.pack_unet_input(a.contiguous(), None if b is None else b.contiguous(), dup, self._cin_pad, self._dtype, out=out, div=div)
 
     @_in_own_f32_mode
     def __call__(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None, cross_attention_kwargs=None,

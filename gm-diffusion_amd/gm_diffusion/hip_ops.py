@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -952,9 +952,11 @@ def cast(x, dtype):
 # ----------------------------------------------------------------------------------------------
 # latent-side
 # ----------------------------------------------------------------------------------------------
-def pack_unet_input(src0, src1, dup, cp, dtype, out=None):
+def pack_unet_input(src0, src1, dup, cp, dtype, out=None, div=None):
     """src0 [B,C0,h,w] (+ src1 [B,C1,h,w]) float32 NCHW -> [dup*B, h*w, cp] channels-last of `dtype`
-    (written into `out` when given: the static input buffer of a captured graph)."""
+    (written into `out` when given: the static input buffer of a captured graph).  ``div`` = (d0, d1): each source is divided by
+    its own float32 divisor before the cast (gmd_pack_unet_input_scaled: a sigma-space scheduler's scale_model_input); None is
+    the plain pack, the launch every other caller makes."""
     _dev(src0, src1, out)
     _f32(src0, "src0")
     _f32(src1, "src1")
@@ -965,8 +967,13 @@ def pack_unet_input(src0, src1, dup, cp, dtype, out=None):
         out = torch.empty((dup * B, hw, cp), dtype=dtype, device=src0.device)
     elif tuple(out.shape) != (dup * B, hw, cp) or out.dtype != dtype:
         raise HipExtensionError("pack_unet_input: `out` has the wrong shape/dtype")
-    check(lib().gmd_pack_unet_input(_ptr(src0), c0, _ptr(src1), c1, B, hw, dup, _ptr(out), cp, dtype_code(dtype), _stream()),
-          "gmd_pack_unet_input")
+    if div is None:
+        check(lib().gmd_pack_unet_input(_ptr(src0), c0, _ptr(src1), c1, B, hw, dup, _ptr(out), cp, dtype_code(dtype), _stream()),
+              "gmd_pack_unet_input")
+    else:
+        d0, d1 = (float(v) for v in div)
+        check(lib().gmd_pack_unet_input_scaled(_ptr(src0), c0, d0, _ptr(src1), c1, d1, B, hw, dup, _ptr(out), cp, dtype_code(dtype),
+                                               _stream()), "gmd_pack_unet_input_scaled")
     return out
 
 
@@ -1085,6 +1092,24 @@ def ddim_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, 
                               float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), int(bool(use_clipped)),
                               sp, dc, sd, pa, p1, _ptr(x_prev), _ptr(x0), _ptr(pred_x0), _stream()), "gmd_ddim_step")
     return x_prev, x0, pred_x0
+
+
+def euler_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, want_pred_x0=False):
+    """Fused CFG + Euler / Euler-ancestral update.  coefs = (sigma_hat, dt, sigma_up); ``noise`` is None for the deterministic
+    scheduler and is added whenever given (also with sigma_up == 0).  Returns (x_prev, pred_x0|None): pred_x0 = x - sigma_hat eps."""
+    _dev(eps_in, x, noise, ratio)
+    for t in (eps_in, x, noise):
+        _f32(t, "latent tensors")
+    if noise is not None and noise.shape != x.shape:
+        raise HipExtensionError("euler_step: noise must have the sample's shape")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    x_prev = torch.empty_like(x)
+    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
+    sh, dt, su = (float(v) for v in coefs)
+    check(lib().gmd_euler_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
+                               float(guidance_rescale), sh, dt, su, _ptr(x_prev), _ptr(pred_x0), _stream()), "gmd_euler_step")
+    return x_prev, pred_x0
 
 
 # ----------------------------------------------------------------------------------------------

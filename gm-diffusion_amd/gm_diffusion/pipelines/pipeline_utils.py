@@ -14,7 +14,8 @@ import os
 
 import torch
 
-from ..components import AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, PNDMScheduler, UNet2DConditionModel
+from ..components import (AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                          EulerDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
 from ..components.configuration import FrozenDict
 
 _LOADABLE = {
@@ -25,6 +26,8 @@ _LOADABLE = {
     "DDPMScheduler": DDPMScheduler,
     "DDIMScheduler": DDIMScheduler,
     "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
+    "EulerDiscreteScheduler": EulerDiscreteScheduler,  # what an SDXL-base checkpoint's scheduler/ folder names
+    "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
 }
 
 

@@ -42,6 +42,14 @@ case (batch 1 + CFG) and also works for batch > 1 and without CFG; with a non-la
 dual_unet.py:1117-1132).  As in the reference the result is always the bare tuple
 ``(sdr, gm)`` and ``return_dict`` is ignored (:1132); ``callback_on_step_end`` is accepted and
 ignored (:1095-1103 is commented out there).
+
+Sigma-space schedulers (``EulerDiscreteScheduler``, ``EulerAncestralDiscreteScheduler``): the reference cannot run one here -- its loop
+indexes ``alphas_cumprod`` with the (float) timestep (:1072) and overwrites the GM state with its scaled copy (:1048) -- so, unlike the
+GM pipeline (which mirrors the reference and divides the whole concatenated input, stable_diffusion_gm.py:1048), this pipeline defines
+the behaviour by the mathematics: the SDR UNet input is ``latents / (sigma**2 + 1) ** 0.5``; ``x0_latent`` is the scheduler's
+``pred_original_sample`` ``x - sigma * eps`` (the VP expression of :1075 in exact arithmetic); the GM UNet input is
+``cat([x0_latent, gm_latents / (sigma**2 + 1) ** 0.5])`` with x0 undivided; neither state is ever scaled.  Fused device path only: the
+generic loop raises a ValueError for such a scheduler.
 """
 from __future__ import annotations
 
@@ -179,7 +187,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             # kernels overlap (the batch-B GM kernels alone cannot fill 256 CUs).
             sdr_stream = torch.cuda.current_stream(latents.device)
             gm_stream = self._gm_stream(latents.device) if self.overlap_streams else sdr_stream
-            ts_host = [int(v) for v in timesteps.tolist()]          # host copy: no device sync inside the loop
+            ts_host = timesteps.tolist()  # host copy: no device sync inside the loop (ints, or a sigma-space scheduler's floats)
             ts_dev = timesteps.to(device=latents.device, dtype=torch.float32)
             g_sdr = g_gm = None
             shared = self._cfg_shared(self.unet, do_cfg)
@@ -198,13 +206,20 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                 # allocated on the caller's stream, consumed (and released) by step 0 on the GM stream: without this the
                 # allocator may hand the block to the SDR stream's step 1 while GM step 0 still reads it
                 gm_latents.record_stream(gm_stream)
+        elif getattr(self.scheduler, "sigma_space", False):
+            raise ValueError(
+                f"{type(self.scheduler).__name__} is a sigma-space scheduler; the dual-UNet pipeline runs it on the fused device path only"
+                " (float32 latents on the GPU with the HIP UNets).  The generic loop restates the reference, which indexes"
+                " alphas_cumprod with the (fractional) timestep and overwrites the GM latents with their scaled copy.")
 
         with self.progress_bar(total=num_inference_steps) as progress_bar:
             for i, t in enumerate(timesteps):
                 if self.interrupt:
                     continue
                 if fused:
-                    x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_sdr.x if g_sdr else None)
+                    div = self._pack_div(self.scheduler, ts_host[i])
+                    x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_sdr.x if g_sdr else None,
+                                             **({"div": (div, 1.0)} if div is not None else {}))
                     self.unet.set_timestep_from(ts_dev, i)
                     if g_sdr:
                         sdr_noise_pred = g_sdr.replay()
@@ -219,7 +234,9 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     with torch.cuda.stream(gm_stream):
                         gm_stream.wait_stream(sdr_stream)  # x0_i is ready
                         x0_latent.record_stream(gm_stream)
-                        gx = self.gm_unet.pack_input((x0_latent, gm_latents), dup=1, out=g_gm.x if g_gm else None)
+                        gm_div = self._pack_div(self.gm_scheduler, ts_host[i])  # x0 is a clean-image estimate: never scaled
+                        gx = self.gm_unet.pack_input((x0_latent, gm_latents), dup=1, out=g_gm.x if g_gm else None,
+                                                     **({"div": (1.0, gm_div)} if gm_div is not None else {}))
                         self.gm_unet.set_timestep_from(ts_dev, i)
                         if g_gm:
                             gm_noise_pred = g_gm.replay()

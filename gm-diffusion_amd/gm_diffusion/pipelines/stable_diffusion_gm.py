@@ -342,10 +342,20 @@ class _GMPipelineBase(DiffusionPipeline):
     def _use_fused(self, latents, unet, scheduler):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
-        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+        from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                                             EulerDiscreteScheduler)
 
-        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler))
+        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler,
+                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler))
                 and isinstance(unet, UNet2DConditionModel))
+
+    @staticmethod
+    def _pack_div(scheduler, timestep):
+        """What the fused loops pass as ``div`` to ``pack_input``: None for the variance-preserving schedulers (their
+        ``scale_model_input`` is the identity: the plain pack, unchanged), the current step's ``(sigma**2 + 1) ** 0.5`` for a
+        sigma-space scheduler (Euler, Euler ancestral), whose ``scale_model_input`` (stable_diffusion_gm.py:1048) is folded into the
+        pack kernel."""
+        return scheduler.input_divisor(timestep) if getattr(scheduler, "sigma_space", False) else None
 
     PREDRAW_NOISE_BYTES = 512 << 20  # ceiling of the pre-drawn scheduler noise (host pinned copy + device copy)
 
@@ -360,12 +370,13 @@ class _GMPipelineBase(DiffusionPipeline):
         of all steps would exceed PREDRAW_NOISE_BYTES (DDPM's default 1000 steps at 1024x1024, batch 8, two schedulers is
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
         DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.  So does a
-        ``DPMSolverMultistepScheduler`` with the SDE algorithm; a deterministic one has nothing to pre-draw.
+        ``DPMSolverMultistepScheduler`` with the SDE algorithm, and ``EulerAncestralDiscreteScheduler`` always; a deterministic
+        scheduler (``EulerDiscreteScheduler`` among them) has nothing to pre-draw.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
-        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler
+        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
 
-        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler))
+        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler, EulerAncestralDiscreteScheduler))
                                  or (isinstance(s_, DPMSolverMultistepScheduler) and s_.draws_noise(None)))
         if generator is None or not all(takes_part(s_) for s_ in schedulers):
             return None
@@ -492,7 +503,9 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
         if fused:
             ctx = self.unet.prepare_context(prompt_embeds)
             sdr_f32 = sdr_latent.to(device=latents.device, dtype=torch.float32).contiguous()
-            ts_host = [int(v) for v in timesteps.tolist()]          # host copy: no device sync inside the loop
+            # host copy: no device sync inside the loop; int64 timesteps stay ints, the float32 (possibly fractional) timesteps of
+            # a sigma-space scheduler stay floats -- never truncated
+            ts_host = timesteps.tolist()
             ts_dev = timesteps.to(device=latents.device, dtype=torch.float32)
             hw = latents.shape[-2:]
             shared = self._cfg_shared(self.unet, do_cfg)
@@ -507,7 +520,9 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
                     continue
                 if fused:
                     # concat(sdr, gm) + CFG duplicate + cast fused into the input pack; CFG/rescale/PLMS in one kernel
-                    x = self.unet.pack_input((sdr_f32, latents), dup=2 if (do_cfg and not shared) else 1, out=graph.x if graph else None)
+                    div = self._pack_div(self.scheduler, ts_host[i])  # gm.py:1048 scales the concatenated tensor: both halves
+                    x = self.unet.pack_input((sdr_f32, latents), dup=2 if (do_cfg and not shared) else 1, out=graph.x if graph else None,
+                                             **({"div": (div, div)} if div is not None else {}))
                     self.unet.set_timestep_from(ts_dev, i)
                     noise_pred = graph.replay() if graph else self.unet.forward_packed(x, nb, hw[0], hw[1], ctx, cfg_shared=shared)
                     latents, _ = self.scheduler.fused_step(noise_pred, ts_host[i], latents, do_cfg, self.guidance_scale,

@@ -242,6 +242,18 @@ int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B
                   float sqrt_alpha, float sqrt_one_minus_alpha,
                   float* x_prev, float* x0, float* pred_x0, gmd_stream_t stream);
 
+/* Euler / Euler-ancestral step (diffusers' EulerDiscreteScheduler and EulerAncestralDiscreteScheduler, epsilon prediction, no
+ * churn) fused with the same CFG combine / rescale as gmd_latent_step, in the float32 operation order of their torch expressions:
+ *   p0 = x - sigma_hat*eps;  d = (x - p0)/sigma_hat;  x_prev = x + d*dt [ + noise*sigma_up when noise != NULL (ancestral) ]
+ * dt = sigma_next - sigma_hat (Euler) or sigma_down - sigma (ancestral), float32 scalars computed by the host exactly as
+ * diffusers computes its 0-dim tensors.  The noise is added whenever it is given, also with sigma_up == 0 (the ancestral
+ * scheduler adds it at every step); it is drawn by the host scheduler from the caller's generator, SDR first, GM second.
+ * pred_x0 (p0: diffusers' pred_original_sample and, in sigma space, the pipeline's x0 that the dual pipeline hands to the GM
+ * UNet) may be NULL.  Refused before any launch: !(sigma_hat > 0), !(sigma_up >= 0) (a NaN is refused), a non-finite dt. */
+int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw,
+                   int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                   float sigma_hat, float dt, float sigma_up, float* x_prev, float* pred_x0, gmd_stream_t stream);
+
 /* per-sample unbiased std of the text eps and of the guided eps -> ratio[b] = std_text/std_cfg
  * (rescale_noise_cfg, stable_diffusion_dual_unet.py:88-91) */
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale,
@@ -253,6 +265,12 @@ int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_sc
  * out [dup*B, HW, CP] of out_dtype with channels >= C0+C1 zeroed. */
 int gmd_pack_unet_input(const float* src0, int C0, const float* src1, int C1, int B, int64_t HW,
                         int dup, void* out, int CP, int out_dtype, gmd_stream_t stream);
+/* gmd_pack_unet_input with each source divided by its own float32 divisor before the one rounding to out_dtype: the
+ * scale_model_input of a sigma-space scheduler (sample / ((sigma**2 + 1) ** 0.5)) folded into the pack.  val = s / div is a
+ * float32 division (no reciprocal multiply), so div == 1.0f reproduces gmd_pack_unet_input bit for bit; padding channels stay
+ * zero.  div0 and (when C1 > 0) div1 must be > 0 (a NaN is refused). */
+int gmd_pack_unet_input_scaled(const float* src0, int C0, float div0, const float* src1, int C1, float div1,
+                               int B, int64_t HW, int dup, void* out, int CP, int out_dtype, gmd_stream_t stream);
 /* [B,HW,ld] (first C channels) of in_dtype -> [B,C,HW] float32 */
 int gmd_unpack_nchw(const void* in, int in_dtype, int64_t ld, int B, int C, int64_t HW,
                     float* out, gmd_stream_t stream);
