@@ -235,6 +235,47 @@ __global__ __launch_bounds__(kThreads) void euler_step_kernel(
     }
 }
 
+// Linear multistep step (diffusers' LMSDiscreteScheduler, epsilon prediction, orders 1-4) fused with the CFG combine, in the
+// operation order of its torch expressions (float32, no FMA contraction):
+//   p0     = x - sigma * eps                pred_original_sample (also the pipeline's x0, as for Euler)
+//   d      = (x - p0) / sigma               derivative; stored to d_out: the host keeps it as the next steps' history
+//   acc    = 0.0f + c0 * d                  Python's sum() starts from int 0, and 0 + (-0.0) is +0.0: the add is a real one
+//   acc    = acc + c1 * d1 [+ c2 * d2 [+ c3 * d3]]      d1, d2, d3: the derivatives of the previous 1, 2, 3 steps
+//   x_prev = x + acc
+// c0..c3 are the integrals of the Lagrange basis polynomials over [sigma, sigma_next], computed by the host in float64 and rounded
+// to float32 once, by the ``float`` argument.  A history pointer beyond order - 1 is never read.
+__global__ __launch_bounds__(kThreads) void lms_step_kernel(
+    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ d1, const float* __restrict__ d2,
+    const float* __restrict__ d3, int B, int64_t chw, int do_cfg, float gs, const float* __restrict__ ratio, float gr, int order,
+    float sigma, float c0, float c1, float c2, float c3, float* __restrict__ d_out, float* __restrict__ x_prev,
+    float* __restrict__ pred_x0) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const int64_t n = (int64_t)B * chw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float eps;
+        if (do_cfg) {
+            const float u = eps_in[i], t = eps_in[n + i];
+            eps = u + gs * (t - u);  // dual.py:1065
+            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
+                const float resc = eps * ratio[i / chw];
+                eps = gr * resc + (1.0f - gr) * eps;
+            }
+        } else {
+            eps = eps_in[i];
+        }
+        const float xt = x[i];
+        const float p0 = xt - sigma * eps;
+        if (pred_x0) pred_x0[i] = p0;
+        const float d = (xt - p0) / sigma;
+        d_out[i] = d;
+        float acc = 0.0f + c0 * d;
+        if (order >= 2) acc = acc + c1 * d1[i];
+        if (order >= 3) acc = acc + c2 * d2[i];
+        if (order >= 4) acc = acc + c3 * d3[i];
+        x_prev[i] = xt + acc;
+    }
+}
+
 // one block per sample: unbiased std over chw of text eps and of the guided eps
 __global__ __launch_bounds__(kThreads) void cfg_std_ratio_kernel(const float* __restrict__ eps_in, int B, int64_t chw,
                                                                  float gs, float* __restrict__ ratio) {
@@ -435,6 +476,28 @@ int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int 
         eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sigma_hat, dt, sigma_up,
         x_prev, pred_x0);
     GMD_CHECK_LAUNCH("gmd_euler_step");
+    return GMD_OK;
+}
+
+int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const float* d2, const float* d3, int B, int64_t chw, int do_cfg,
+                 float guidance_scale, const float* rescale_ratio, float guidance_rescale, int order, float sigma, float c0, float c1,
+                 float c2, float c3, float* d_out, float* x_prev, float* pred_x0, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && chw > 0, "gmd_lms_step: bad shape B=%d chw=%lld", B, (long long)chw);
+    GMD_REQUIRE(order >= 1 && order <= 4, "gmd_lms_step: order %d not in 1..4", order);
+    // written as (v > 0) so that a NaN is refused too
+    GMD_REQUIRE(sigma > 0.0f, "gmd_lms_step: sigma must be > 0 (got %g)", (double)sigma);
+    const float c[4] = {c0, c1, c2, c3};
+    for (int k = 0; k < order; ++k)  // a coefficient beyond the order is never used
+        GMD_REQUIRE(std::isfinite(c[k]), "gmd_lms_step: coefficient c%d must be finite (got %g)", k, (double)c[k]);
+    if (B == 0) return GMD_OK;
+    GMD_REQUIRE(eps_in && x && d_out && x_prev, "gmd_lms_step: null pointer");
+    GMD_REQUIRE(order < 2 || d1, "gmd_lms_step: order %d needs d1", order);
+    GMD_REQUIRE(order < 3 || d2, "gmd_lms_step: order %d needs d2", order);
+    GMD_REQUIRE(order < 4 || d3, "gmd_lms_step: order 4 needs d3");
+    lms_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
+        eps_in, x, d1, d2, d3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, order, sigma, c0, c1,
+        c2, c3, d_out, x_prev, pred_x0);
+    GMD_CHECK_LAUNCH("gmd_lms_step");
     return GMD_OK;
 }
 

@@ -2,8 +2,8 @@
 Schedulers for the MI355X build: ``PNDMScheduler`` (PLMS, the "50 PNDM steps" configuration of
 scripts/stage2/train_gm_unet.py:171-176), ``DDPMScheduler`` (scripts/inference/generate_hdr.py:162),
 ``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188),
-``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` (the only ones
-whose ``init_noise_sigma`` and ``scale_model_input`` do something).  In the reference they come from ``diffusers``; these
+``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` /
+``LMSDiscreteScheduler`` (the only ones whose ``init_noise_sigma`` and ``scale_model_input`` do something).  In the reference they come from ``diffusers``; these
 classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241, 610-625, 715,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
 access), ``set_timesteps``, ``timesteps``, ``order``, ``init_noise_sigma``,
@@ -1004,3 +1004,124 @@ class EulerAncestralDiscreteScheduler(_SigmaSchedulerBase):
             noise = randn_tensor(model_output.shape, generator=generator, device=dev, dtype=model_output.dtype)
         prev = prev + noise * sigma_up
         return self._finish(prev.to(model_output.dtype), p0, return_dict)
+
+
+# 4-point Gauss-Legendre rule on [-1, 1]: +-_GL_X[k] with weight _GL_W[k].  Exact for polynomials of degree <= 7; the LMS basis
+# polynomials have degree <= 3.  The two weights sum to exactly 1.0 in float64, so a constant integrand (order 1) gives b - a exactly.
+_GL_X = (0.8611363115940526, 0.3399810435848563)
+_GL_W = (0.34785484513745385, 0.6521451548625461)
+
+
+class LMSDiscreteScheduler(_SigmaSchedulerBase):
+    """Linear multistep (Adams-Bashforth in sigma, k-diffusion's ``sample_lms`` as diffusers restates it), orders 1-4: the update is
+    ``sample + sum_j c_j d_j`` over the derivatives ``d = (sample - pred_original_sample) / sigma`` of this step and of up to three
+    earlier ones, with ``c_j`` the integral over [sigma, sigma_next] of the j-th Lagrange basis polynomial on the last ``order``
+    sigmas.  One UNet evaluation per step, no noise.  Tables, spacings, Karras / custom sigmas, ``init_noise_sigma``,
+    ``scale_model_input`` and the limits (epsilon prediction only, no exponential / beta sigmas) are ``_SigmaSchedulerBase``'s.
+    ``step`` / ``fused_step`` run as ONE HIP kernel (gmd_lms_step) for float32 device tensors, as diffusers' torch expressions
+    (``_host_step``) otherwise.
+
+    Unlike diffusers (``scipy.integrate.quad(..., epsrel=1e-4)`` on an integrand evaluated through float32 0-d tensors), the
+    coefficients take the float32 sigmas as float64 and integrate the product form of the basis with a 4-point Gauss-Legendre
+    rule, which is exact for these polynomials up to float64 rounding; each is rounded to float32 once, where it meets the
+    derivative."""
+
+    _name = "LMSDiscreteScheduler"
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False, prediction_type="epsilon",
+                     timestep_spacing="linspace", steps_offset=0)
+    MAX_ORDER = 4  # gmd_lms_step reads at most three earlier derivatives
+
+    def __init__(self, **kwargs):
+        self._init_sigma_space(kwargs)
+        self.derivatives = []
+
+    def set_timesteps(self, num_inference_steps=None, device=None, timesteps=None, sigmas=None):
+        super().set_timesteps(num_inference_steps, device=device, timesteps=timesteps, sigmas=sigmas)
+        self._sig64 = self.sigmas.numpy().astype(np.float64).tolist()
+        self.derivatives = []
+
+    def draws_noise(self, timestep):
+        """False: the step is deterministic and never consumes a generator."""
+        return False
+
+    def get_lms_coefficient(self, order, t, current_order):
+        """The integral over [sigma_t, sigma_{t+1}] of the Lagrange basis polynomial that is 1 at sigma_{t - current_order} and 0 at
+        the other nodes sigma_{t-k}, k < order, as a Python float (float64).  The integrand stays in product form: expanded into
+        monomial coefficients it would lose four digits to cancellation."""
+        if not 0 <= current_order < order <= t + 1:
+            raise ValueError(f"{self._name}: no coefficient {current_order} of order {order} at step {t}")
+        s = self._sig64 if self.num_inference_steps is not None else self.sigmas.numpy().astype(np.float64).tolist()
+        a, b = s[t], s[t + 1]
+        mid, half = 0.5 * (a + b), 0.5 * (b - a)
+        node = s[t - current_order]
+        others = [s[t - k] for k in range(order) if k != current_order]
+
+        def basis(tau):
+            prod = 1.0
+            for o in others:
+                prod *= (tau - o) / (node - o)
+            return prod
+
+        total = 0.0
+        for gx, gw in zip(_GL_X, _GL_W):
+            total += gw * (basis(mid - half * gx) + basis(mid + half * gx))
+        return half * total
+
+    def _plan(self, timestep, order):
+        """(sigma as a float32 0-d tensor, effective order k, [c_0 .. c_{k-1}] as Python floats) of the next step.  k is
+        ``min(step_index + 1, order)``, and never more than the history allows (one more than the derivatives kept, which differs
+        from ``step_index`` only when the caller raises ``order`` in mid-trajectory)."""
+        order = int(order)
+        if not 1 <= order <= self.MAX_ORDER:
+            raise ValueError(f"{self._name}: order must be in 1..{self.MAX_ORDER} (got {order})")
+        sigma = self._sigma(timestep)
+        i = self._step_index
+        k = min(i + 1, order, len(self.derivatives) + 1)
+        return sigma, k, [self.get_lms_coefficient(k, i, j) for j in range(k)]
+
+    def _keep(self, derivative, order):
+        self.derivatives.append(derivative)
+        del self.derivatives[:-int(order)]
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, order=4):
+        """One HIP kernel pass (gmd_lms_step): CFG combine (+rescale), x0 prediction, the derivative and the multistep update.  The
+        derivative kept as history is the kernel's own output, never ``eps_in`` (which may be the static output buffer of a captured
+        graph that the next replay overwrites).  Returns (prev_sample, pred_original_sample | None)."""
+        sigma, k, coeffs = self._plan(timestep, order)
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        hist = list(reversed(self.derivatives))[:k - 1]
+        d, prev, p0 = ops.lms_step(eps_in.contiguous(), sample.contiguous(), k, [sigma.item()] + coeffs + [0.0] * (4 - k), do_cfg,
+                                   guidance_scale, hist=hist, ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
+        self._keep(d, order)
+        self._step_index += 1
+        return prev, p0
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None,
+                   order=4):
+        """Same contract as ``EulerDiscreteScheduler.fused_step`` (device float32 tensors only); ``generator`` and ``noise`` are
+        accepted and unused.  Returns (prev_sample, x0 | None) with x0 = ``sample - sigma * eps``."""
+        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, order)
+
+    def step(self, model_output, timestep, sample, order=4, return_dict=True, **ignored):
+        """diffusers' signature.  ``generator`` and ``noise``, which the pipelines hand to the stochastic schedulers, are accepted
+        as keywords and ignored; they are not named parameters, so ``prepare_extra_step_kwargs`` (which reads this signature)
+        passes neither, as for diffusers' class."""
+        bad = [k for k in ignored if k not in ("generator", "noise")]
+        if bad:
+            raise TypeError(f"{self._name}.step: unexpected arguments {bad}")
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, order)
+            return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+        return self._host_step(model_output, timestep, sample, order, return_dict)
+
+    def _host_step(self, model_output, timestep, sample, order=4, return_dict=True):
+        """The torch expressions of diffusers' ``LMSDiscreteScheduler.step`` (host tensors; also the reference for the kernel test).
+        ``sum`` starts from the int 0, so the first addition is ``0 + c_0 * d``."""
+        sigma, k, lms_coeffs = self._plan(timestep, order)
+        sigma = sigma.to(model_output.device)
+        p0 = sample - sigma * model_output
+        derivative = (sample - p0) / sigma
+        self._keep(derivative, order)
+        prev = sample + sum(coeff * derivative for coeff, derivative in zip(lms_coeffs, reversed(self.derivatives)))
+        return self._finish(prev, p0, return_dict)

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -1110,6 +1110,32 @@ def euler_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None,
     check(lib().gmd_euler_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
                                float(guidance_rescale), sh, dt, su, _ptr(x_prev), _ptr(pred_x0), _stream()), "gmd_euler_step")
     return x_prev, pred_x0
+
+
+def lms_step(eps_in, x, order, coefs, do_cfg, guidance_scale, hist=(), ratio=None, guidance_rescale=0.0, want_pred_x0=False):
+    """Fused CFG + linear multistep (LMS, orders 1-4) update.  coefs = (sigma, c0, c1, c2, c3); ``hist``: the derivatives of the
+    previous steps, newest first, of which the first order - 1 are read.  Returns (d, x_prev, pred_x0|None): d = the step's
+    derivative, pred_x0 = x - sigma eps.  The three outputs are allocated here, so the derivative the caller keeps as history is
+    never the static buffer of a captured graph."""
+    _dev(eps_in, x, ratio, *hist)
+    for t in (eps_in, x, *hist):
+        _f32(t, "latent tensors")
+    order = int(order)
+    if len(hist) < order - 1:
+        raise HipExtensionError(f"lms_step: order {order} needs {order - 1} earlier derivatives (got {len(hist)})")
+    if any(h.shape != x.shape for h in hist):
+        raise HipExtensionError("lms_step: a history tensor must have the sample's shape")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    d = torch.empty_like(x)
+    x_prev = torch.empty_like(x)
+    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
+    h = list(hist[:3]) + [None] * (3 - len(hist[:3]))
+    sg, c0, c1, c2, c3 = (float(v) for v in coefs)
+    check(lib().gmd_lms_step(_ptr(eps_in), _ptr(x), _ptr(h[0]), _ptr(h[1]), _ptr(h[2]), B, chw, int(do_cfg), float(guidance_scale),
+                             _ptr(ratio), float(guidance_rescale), order, sg, c0, c1, c2, c3, _ptr(d), _ptr(x_prev), _ptr(pred_x0),
+                             _stream()), "gmd_lms_step")
+    return d, x_prev, pred_x0
 
 
 # ----------------------------------------------------------------------------------------------

@@ -15,7 +15,7 @@ import os
 import torch
 
 from ..components import (AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                          EulerDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
+                          EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
 from ..components.configuration import FrozenDict
 
 _LOADABLE = {
@@ -28,6 +28,7 @@ _LOADABLE = {
     "DPMSolverMultistepScheduler": DPMSolverMultistepScheduler,
     "EulerDiscreteScheduler": EulerDiscreteScheduler,  # what an SDXL-base checkpoint's scheduler/ folder names
     "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
+    "LMSDiscreteScheduler": LMSDiscreteScheduler,
 }
 
 

@@ -43,7 +43,7 @@ dual_unet.py:1117-1132).  As in the reference the result is always the bare tupl
 ``(sdr, gm)`` and ``return_dict`` is ignored (:1132); ``callback_on_step_end`` is accepted and
 ignored (:1095-1103 is commented out there).
 
-Sigma-space schedulers (``EulerDiscreteScheduler``, ``EulerAncestralDiscreteScheduler``): the reference cannot run one here -- its loop
+Sigma-space schedulers (``EulerDiscreteScheduler``, ``EulerAncestralDiscreteScheduler``, ``LMSDiscreteScheduler``): the reference cannot run one here -- its loop
 indexes ``alphas_cumprod`` with the (float) timestep (:1072) and overwrites the GM state with its scaled copy (:1048) -- so, unlike the
 GM pipeline (which mirrors the reference and divides the whole concatenated input, stable_diffusion_gm.py:1048), this pipeline defines
 the behaviour by the mathematics: the SDR UNet input is ``latents / (sigma**2 + 1) ** 0.5``; ``x0_latent`` is the scheduler's

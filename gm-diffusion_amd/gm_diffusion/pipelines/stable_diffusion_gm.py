@@ -343,17 +343,17 @@ class _GMPipelineBase(DiffusionPipeline):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
         from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                                             EulerDiscreteScheduler)
+                                             EulerDiscreteScheduler, LMSDiscreteScheduler)
 
         return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler,
-                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler))
+                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler))
                 and isinstance(unet, UNet2DConditionModel))
 
     @staticmethod
     def _pack_div(scheduler, timestep):
         """What the fused loops pass as ``div`` to ``pack_input``: None for the variance-preserving schedulers (their
         ``scale_model_input`` is the identity: the plain pack, unchanged), the current step's ``(sigma**2 + 1) ** 0.5`` for a
-        sigma-space scheduler (Euler, Euler ancestral), whose ``scale_model_input`` (stable_diffusion_gm.py:1048) is folded into the
+        sigma-space scheduler (Euler, Euler ancestral, LMS), whose ``scale_model_input`` (stable_diffusion_gm.py:1048) is folded into the
         pack kernel."""
         return scheduler.input_divisor(timestep) if getattr(scheduler, "sigma_space", False) else None
 
@@ -371,7 +371,7 @@ class _GMPipelineBase(DiffusionPipeline):
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
         DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.  So does a
         ``DPMSolverMultistepScheduler`` with the SDE algorithm, and ``EulerAncestralDiscreteScheduler`` always; a deterministic
-        scheduler (``EulerDiscreteScheduler`` among them) has nothing to pre-draw.
+        scheduler (``EulerDiscreteScheduler`` and ``LMSDiscreteScheduler`` among them) has nothing to pre-draw.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
         from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler

@@ -254,6 +254,21 @@ int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int 
                    int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
                    float sigma_hat, float dt, float sigma_up, float* x_prev, float* pred_x0, gmd_stream_t stream);
 
+/* Linear multistep step (diffusers' LMSDiscreteScheduler, epsilon prediction, orders 1-4) fused with the same CFG combine /
+ * rescale as gmd_latent_step, in the float32 operation order of its torch expressions:
+ *   p0 = x - sigma*eps;  d = (x - p0)/sigma;  acc = 0.0f + c0*d [+ c1*d1 [+ c2*d2 [+ c3*d3]]];  x_prev = x + acc
+ * d1, d2, d3 are the derivatives of the previous 1, 2, 3 steps (d_out of those launches); d(order) and beyond are never
+ * read, nor are their coefficients.  The sum starts from 0.0f because Python's sum() starts from int 0: 0 + (-0.0) is +0.0.
+ * c0..c3 are the integrals over [sigma, sigma_next] of the Lagrange basis polynomials on the last `order` sigmas, computed by
+ * the host in float64 and rounded to float32 by this argument.  d_out (the derivative, which the host keeps as history) and
+ * x_prev are always written; pred_x0 (p0: diffusers' pred_original_sample and the pipeline's x0) may be NULL.  d_out must
+ * not alias an input.  Refused before any launch: order outside 1..4, !(sigma > 0) (a NaN is refused), a non-finite
+ * coefficient among c0..c(order-1), a null d1..d(order-1). */
+int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const float* d2, const float* d3, int B, int64_t chw,
+                 int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                 int order, float sigma, float c0, float c1, float c2, float c3,
+                 float* d_out, float* x_prev, float* pred_x0, gmd_stream_t stream);
+
 /* per-sample unbiased std of the text eps and of the guided eps -> ratio[b] = std_text/std_cfg
  * (rescale_noise_cfg, stable_diffusion_dual_unet.py:88-91) */
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale,
