@@ -1223,14 +1223,22 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
             const int n = n0 + srow + RPP * i;
             woff[i] = n < p.N ? (unsigned)n * (unsigned)p.ldw * 2u + (unsigned)chunk * 16u : kOOB;
         }
+        // K position of the conv loader: (channel block cb0, tap 0..8, channel c0); tap == 9 is the K tail (GemmParams::A2), whose
+        // c0 counts the channels of A2 from 0.  All of it is wave-uniform.
         int tap = 0, c0 = 0, cb0 = 0;
         bool newtap = true;
         if (CONV) {
-            const int sb = p.cblk / BK, per_cb = 9 * sb;
-            const int cbi = kt_begin / per_cb, rem = kt_begin - cbi * per_cb;
-            tap = rem / sb;
-            cb0 = cbi * p.cblk;
-            c0 = cb0 + (rem - tap * sb) * BK;
+            const int sb = p.cblk / BK, per_cb = 9 * sb, nconv = 9 * (p.Cin / BK);
+            if (kt_begin >= nconv) {  // this slice starts inside the tail
+                tap = 9;
+                cb0 = p.Cin;
+                c0 = (kt_begin - nconv) * BK;
+            } else {
+                const int cbi = kt_begin / per_cb, rem = kt_begin - cbi * per_cb;
+                tap = rem / sb;
+                cb0 = cbi * p.cblk;
+                c0 = cb0 + (rem - tap * sb) * BK;
+            }
         }
         const unsigned lds_base = __builtin_amdgcn_readfirstlane((unsigned)(size_t)(__attribute__((address_space(3))) void*)smem);
         u32x4 dA, dW;
@@ -1240,6 +1248,12 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
                        (unsigned)__builtin_amdgcn_readfirstlane(p.a_bytes), 0x00020000u};
             dW = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)bw), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(bw >> 32) & 0xffffu),
                        (unsigned)__builtin_amdgcn_readfirstlane(p.w_bytes), 0x00020000u};
+        }
+        u32x4 dA2 = dA;  // the K tail's operand (CONV with K2 > 0 only; never selected otherwise)
+        if (CONV && p.K2 > 0) {
+            const uint64_t b2 = (uint64_t)p.A2;
+            dA2 = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b2), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b2 >> 32) & 0xffffu),
+                        (unsigned)__builtin_amdgcn_readfirstlane(p.a2_bytes), 0x00020000u};
         }
         auto dma16 = [&](const u32x4& desc, unsigned lds_addr, unsigned voff, unsigned soff) {
 #pragma clang diagnostic push
@@ -1256,30 +1270,42 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
             constexpr int lo = Q == 4 ? 0 : Q * NP / 4, hi = Q == 4 ? NP : (Q + 1) * NP / 4;
             unsigned kbytes = (unsigned)(kt_begin + kt) * (BK * 2);
             unsigned abytes = kbytes;
+            const bool tail = CONV && tap == 9;  // wave-uniform: the descriptor below is a scalar select
             if (CONV) {
                 if ((Q == 0 || Q == 4) && newtap) {
-                    const int ky = tap / 3, kx = tap - ky * 3;
+                    if (tail) {  // rows of A2 at the output pixel itself
 #pragma unroll
-                    for (int i = 0; i < NA; ++i) aoff[i] = conv_tap_offset<CONV>(p, pv[i], pb[i], py[i], px[i], ky, kx, chunk);
+                        for (int i = 0; i < NA; ++i)
+                            aoff[i] = pv[i] ? (unsigned)(m0 + srow + RPP * i) * (unsigned)p.lda2 * 2u + (unsigned)chunk * 16u : kOOB;
+                    } else {
+                        const int ky = tap / 3, kx = tap - ky * 3;
+#pragma unroll
+                        for (int i = 0; i < NA; ++i) aoff[i] = conv_tap_offset<CONV>(p, pv[i], pb[i], py[i], px[i], ky, kx, chunk);
+                    }
                     newtap = false;
                 }
                 abytes = (unsigned)c0 * 2u;
-                kbytes = (unsigned)(tap * p.Cin + c0) * 2u;
+                kbytes = (unsigned)((tail ? 9 * p.Cin : tap * p.Cin) + c0) * 2u;
             }
+            const u32x4 dAs = tail ? dA2 : dA;
             const unsigned stage = lds_base + (unsigned)stage_idx * kStage + (unsigned)lw * (8 * 128);
 #pragma unroll
             for (int i = 0; i < NA; ++i)
-                if (i >= lo && i < hi) dma16(dA, stage + i * (RPP * 128), aoff[i], abytes);
+                if (i >= lo && i < hi) dma16(dAs, stage + i * (RPP * 128), aoff[i], abytes);
 #pragma unroll
             for (int i = 0; i < NW; ++i)
                 if (NA + i >= lo && NA + i < hi) dma16(dW, stage + BM * 128 + i * (RPP * 128), woff[i], kbytes);
             if (CONV && (Q == 3 || Q == 4)) {
                 c0 += BK;
-                if (c0 >= cb0 + p.cblk) {
+                if (tap < 9 && c0 >= cb0 + p.cblk) {
                     c0 = cb0;
                     ++tap;
                     newtap = true;
-                    if (tap == 9) { tap = 0; cb0 += p.cblk; c0 = cb0; }
+                    if (tap == 9) {
+                        cb0 += p.cblk;
+                        if (cb0 >= p.Cin) c0 = 0;            // the taps are done: what follows (if anything) is the tail
+                        else { tap = 0; c0 = cb0; }
+                    }
                 }
             }
         };
@@ -2013,12 +2039,17 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
     const int npieces = (patch_px + 7) >> 3;
     const int PB = npieces * 1024;                    // bytes of one patch buffer
     const int b0 = m0 / HW, r0 = HW >= BM ? (m0 - b0 * HW) / W : 0;
-    // K range of this slice, in 64-channel blocks
-    const int nblk_total = p.Cin / BK;
+    // K range of this slice, in 64-channel blocks: the Cin / 64 blocks of A (nine K steps each, one per tap), then the K2 / 64 blocks of the
+    // K tail (GemmParams::A2; ONE K step each: a block's "patch" is read at the centre tap only)
+    const int nconvb = p.Cin / BK;
+    const int nblk_total = nconvb + p.K2 / BK;
     const int per = (nblk_total + p.ksplit - 1) / p.ksplit;
     const int cb_begin = ks * per;
     const int ncb = (cb_begin + per <= nblk_total ? per : nblk_total - cb_begin);  // blocks of this slice (may be <= 0)
-    const int nk = ncb * 9;
+    const int ncv = ncb <= 0 ? 0 : (nconvb - cb_begin < 0 ? 0 : (nconvb - cb_begin < ncb ? nconvb - cb_begin : ncb));  // ... of them over A
+    const int ntl = ncb <= 0 ? 0 : ncb - ncv;                                                                          // ... and in the tail
+    const int tail_begin = cb_begin > nconvb ? cb_begin - nconvb : 0;   // first tail block of this slice
+    const int nk = ncv * 9 + ntl;
 
     auto seg_barrier = [&]() {
         __builtin_amdgcn_sched_barrier(0);
@@ -2033,7 +2064,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
         const int ltid = tid - NCONS * 64;
         // patch pieces of this wave: piece q = j * 4 + lw; a piece beyond the patch re-loads an early piece (same bytes to the same
         // place: harmless) so that every wave issues exactly NPP pieces per block and the counted waits below hold
-        unsigned poff[NPP];
+        unsigned poff[NPP], poff2[NPP];  // poff2: the same patch pixels in A2 (rows of lda2 elements; the halo is never read: zeros)
 #pragma unroll
         for (int j = 0; j < NPP; ++j) {
             int q = j * LW + lw;
@@ -2045,6 +2076,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
             const int iy = r0 + pr - 1, ix = pc - 1, b = b0 + i;
             const bool ok = pix < patch_px && b < p.M / HW && iy >= 0 && iy < H && ix >= 0 && ix < W;
             poff[j] = ok ? (unsigned)(((b * H + iy) * W + ix) * p.Cin) * 2u + (unsigned)chunk * 16u : kOOB;
+            poff2[j] = ok && p.K2 > 0 ? (unsigned)((b * H + iy) * W + ix) * (unsigned)p.lda2 * 2u + (unsigned)chunk * 16u : kOOB;
         }
         unsigned woff[NWP];
         {
@@ -2064,6 +2096,12 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
             dW = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)bw), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(bw >> 32) & 0xffffu),
                        (unsigned)__builtin_amdgcn_readfirstlane(p.w_bytes), 0x00020000u};
         }
+        u32x4 dA2 = dA;  // the K tail's operand (never selected without one)
+        if (p.K2 > 0) {
+            const uint64_t b2 = (uint64_t)p.A2;
+            dA2 = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b2), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b2 >> 32) & 0xffffu),
+                        (unsigned)__builtin_amdgcn_readfirstlane(p.a2_bytes), 0x00020000u};
+        }
         auto dma16 = [&](const u32x4& desc, unsigned lds_addr, unsigned voff, unsigned soff) {
 #pragma clang diagnostic push
 #pragma clang diagnostic ignored "-Winline-asm"
@@ -2073,22 +2111,26 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
                          : "memory", "m0");
 #pragma clang diagnostic pop
         };
-        // patch pieces [lo, hi) of this wave for 64-channel block cb into patch buffer `buf`
+        // patch pieces [lo, hi) of this wave for block cb of the slice (cb >= ncv: a tail block, from A2) into patch buffer `buf`
         auto dma_patch = [&](auto LO, auto HI, int cb, int buf) {
             constexpr int lo = decltype(LO)::value, hi = decltype(HI)::value;
-            const unsigned soff = (unsigned)(cb_begin + cb) * (BK * 2);
+            const bool tl = cb >= ncv;  // wave-uniform: the descriptor is a scalar select
+            const unsigned soff = (unsigned)(tl ? tail_begin + cb - ncv : cb_begin + cb) * (BK * 2);
+            const u32x4 d = tl ? dA2 : dA;
 #pragma unroll
             for (int j = 0; j < NPP; ++j)
                 if (j >= lo && j < hi) {
                     int q = j * LW + lw;
                     if (q >= npieces) q -= npieces;
-                    dma16(dA, lds_base + (unsigned)buf * (unsigned)PB + (unsigned)q * 1024u, poff[j], soff);
+                    dma16(d, lds_base + (unsigned)buf * (unsigned)PB + (unsigned)q * 1024u, tl ? poff2[j] : poff[j], soff);
                 }
         };
-        // W pieces [lo, hi) of K step (cb, tap) into ring stage `st`
-        auto dma_w = [&](auto LO, auto HI, int cb, int tap, int st) {
+        // W pieces [lo, hi) of K step kt of the slice into ring stage `st`: (block kt / 9, tap kt % 9) over A, then one step per tail block
+        auto dma_w = [&](auto LO, auto HI, int kt, int st) {
             constexpr int lo = decltype(LO)::value, hi = decltype(HI)::value;
-            const unsigned soff = (unsigned)(tap * p.Cin + (cb_begin + cb) * BK) * 2u;
+            const int wcb = kt / 9, wtap = kt - wcb * 9;
+            const unsigned soff = kt < ncv * 9 ? (unsigned)(wtap * p.Cin + (cb_begin + wcb) * BK) * 2u
+                                               : (unsigned)(9 * p.Cin + (tail_begin + kt - ncv * 9) * BK) * 2u;
             const unsigned stage = lds_base + w_ring + (unsigned)st * kWStage + (unsigned)lw * (8 * 128);
 #pragma unroll
             for (int i = 0; i < NWP; ++i)
@@ -2097,13 +2139,17 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
         // patch pieces issued at tap t of a block (for the NEXT block): 2,2,2,2,2,1,1,1,0 (NPP = 13) / 2,2,2,1,1,1,1,1,0 (NPP = 11)
         if (nk > 0) {
             dma_patch(IntC<0>{}, IntC<NPP>{}, 0, 0);
-            dma_w(IntC<0>{}, IntC<NWP>{}, 0, 0, 0);
-            dma_w(IntC<0>{}, IntC<NWP>{}, 0, 1, 1);
-            wait_vmcnt<NWP>();  // the patch of block 0 and the W tile of step 0 have landed
+            dma_w(IntC<0>{}, IntC<NWP>{}, 0, 0);
+            if (nk > 1) {       // (a slice of ONE tail block has no second step)
+                dma_w(IntC<0>{}, IntC<NWP>{}, 1, 1);
+                wait_vmcnt<NWP>();  // the patch of block 0 and the W tile of step 0 have landed
+            } else {
+                wait_vmcnt<0>();
+            }
             seg_barrier();      // #0
             int st_fill = 2;
-            for (int cb = 0; cb < ncb; ++cb) {
-                const bool next_blk = cb + 1 < ncb;
+            for (int cb = 0; cb < ncv; ++cb) {
+                const bool next_blk = cb + 1 < ncb;  // (the next block may be the first of the tail: same pieces, from A2)
                 const int nbuf = (cb + 1) & 1;
                 auto kstep = [&](auto TAP) {
                     constexpr int t = decltype(TAP)::value;
@@ -2111,10 +2157,9 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
                     constexpr int pc = t < n2 ? 2 : (t < 8 ? 1 : 0);      // patch pieces issued at this tap
                     constexpr int pj = t < n2 ? 2 * t : n2 + t;           // index of the first of them
                     const int kt = cb * 9 + t;
-                    // the W tile of step kt+2: (cb, t+2) or the next block's (t+2-9)
+                    // the W tile of step kt+2: (cb, t+2), the next block's (t+2-9), or a tail step's
                     const bool more = kt + 2 < nk;
-                    const int wcb = t + 2 < 9 ? cb : cb + 1, wtap = t + 2 < 9 ? t + 2 : t + 2 - 9;
-                    if (more) dma_w(IntC<0>{}, IntC<NWP>{}, wcb, wtap, st_fill);
+                    if (more) dma_w(IntC<0>{}, IntC<NWP>{}, kt + 2, st_fill);
                     if (next_blk && pc >= 1) dma_patch(IntC<pj>{}, IntC<pj + pc>{}, cb + 1, nbuf);
                     // everything issued BEFORE this K step has landed (the W tile of step kt+1; at tap 8, pc == 0: the whole patch
                     // of the next block): only this step's own pieces may remain
@@ -2126,6 +2171,23 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
                 };
                 kstep(IntC<0>{}); kstep(IntC<1>{}); kstep(IntC<2>{}); kstep(IntC<3>{}); kstep(IntC<4>{});
                 kstep(IntC<5>{}); kstep(IntC<6>{}); kstep(IntC<7>{}); kstep(IntC<8>{});
+            }
+            // K tail: one K step per block, so the NEXT tail block's whole patch is issued in this step, IN FRONT of the W tile of step
+            // kt+2, and the counted wait leaves only those W pieces outstanding: the patch (and everything older: the W tile of step
+            // kt+1) has landed at B(kt+1).  Its buffer was last read in the step before this one, whose reads returned before B(kt).
+            // No prefetch distance: a tail step pays its patch's load latency (this kernel is the non-default patch mode).
+            for (int tb = 0; tb < ntl; ++tb) {
+                const int kt = ncv * 9 + tb;
+                const bool more = kt + 2 < nk;
+                if (tb + 1 < ntl) dma_patch(IntC<0>{}, IntC<NPP>{}, ncv + tb + 1, (ncv + tb + 1) & 1);
+                if (more) {
+                    dma_w(IntC<0>{}, IntC<NWP>{}, kt + 2, st_fill);
+                    wait_vmcnt<NWP>();
+                } else {
+                    wait_vmcnt<0>();
+                }
+                seg_barrier();  // B(kt+1)
+                st_fill = st_fill == NWS - 1 ? 0 : st_fill + 1;
             }
         }
         __syncthreads();
@@ -2168,7 +2230,7 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
     };
     if (nk > 0) {
         seg_barrier();                  // B(0): the patch of block 0 and W tile 0 are in LDS
-        int wst = 0, pbuf = 0, tap = 0, kx = 0, tapoff = 0;
+        int wst = 0, pbuf = 0, tap = 0, kx = 0, tapoff = ncv > 0 ? 0 : PW + 1;  // (a tail block is read at the centre tap)
         for (int kt = 0; kt < nk; ++kt) {
             frag_reads(pbuf, tapoff, wst, 0, fa0, fb0);
             frag_reads(pbuf, tapoff, wst, 1, fa1, fb1);   // the second half step's reads return under the first one's MFMAs
@@ -2176,10 +2238,13 @@ __global__ __launch_bounds__(768, 3) void conv_patch_cont_kernel(const GemmParam
             mfmas(fa1, fb1);
             seg_barrier();              // B(kt+1)
             wst = wst == NWS - 1 ? 0 : wst + 1;
-            ++tap;
-            if (tap == 9) { tap = 0; kx = 0; tapoff = 0; pbuf ^= 1; }
-            else if (kx == 2) { kx = 0; tapoff += PW - 2; }
-            else { ++kx; ++tapoff; }
+            if (kt + 1 >= ncv * 9) { pbuf ^= 1; tapoff = PW + 1; }  // the next step (if any) is a tail block of its own
+            else {
+                ++tap;
+                if (tap == 9) { tap = 0; kx = 0; tapoff = 0; pbuf ^= 1; }
+                else if (kx == 2) { kx = 0; tapoff += PW - 2; }
+                else { ++kx; ++tapoff; }
+            }
         }
     }
     const int z = 0;
@@ -2374,6 +2439,12 @@ int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t
         gmd_set_error("%s: plan %dx%d pf=%d ksplit=%d (M=%d N=%d bucket=%d) %s", name, pl.bm, pl.bn, pl.pf, pl.ksplit, p.M, p.N, p.cs_bucket, why);
         return GMD_ERR_UNSUPPORTED;
     }
+    if (CONV && p.K2 > 0 && !(pl.pf == kPingPong && pl.bm == 256 && (pl.bn == 160 || pl.bn == 128))) {
+        // the K tail lives in the loader of gemm_pp_kernel<CONV> only: the caller issues the two launches it replaces
+        gmd_set_error("%s: plan %dx%d pf=%d has no K-tail loader (M=%d N=%d K=%d): only the 256-row ping-pong kernel does", name, pl.bm, pl.bn,
+                      pl.pf, p.M, p.N, p.K);
+        return GMD_ERR_INVALID;
+    }
     p.ksplit = pl.ksplit;
     p.ws = (float*)ws;
     p.tile_group = CONV ? 1 : pick_tile_group(pl, p.M, p.N, p.K);  // (convolutions: neighbouring M-panels share their halo rows)
@@ -2392,7 +2463,7 @@ int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t
         else if (pl.bm == 64 && pl.bn == 128) e = launch_lc<HT, CONV, 2, 4>(p, gz, s);
         else { gmd_set_error("%s: loader/consumer tile %dx%d is not instantiated", name, pl.bm, pl.bn); return GMD_ERR_UNSUPPORTED; }
         done = true;
-    } else if (CONV && use_conv_patch(cfg, pl, p)) {
+    } else if (CONV && (p.K2 == 0 || cfg.conv_patch_mode == 2) && use_conv_patch(cfg, pl, p)) {  // (K tail: the continuous form only; mode 1 -> per-tap)
         // ping-pong structure with the input patch resident in LDS (conv_patch_kernel): same tiles, same epilogues, same plan code
         if (pl.bn == 160) e = launch_conv_patch<HT, 5>(p, cfg.conv_patch_mode == 2, gz, s);
         else if (pl.bn == 128) e = launch_conv_patch<HT, 4>(p, cfg.conv_patch_mode == 2, gz, s);
@@ -2588,7 +2659,7 @@ struct GnTail {
 int conv3x3_impl(const void* X, const void* Wt, void* Y, int dtype, int out_dtype, int B, int Hin, int Win, int Cin, int Cout,
                  int stride, int upsample, int pad_mode, const float* bias, const float* rowbias, int64_t ldrb, const void* residual,
                  float alpha, float* colstats, int colstats_bucket, void* workspace, int64_t workspace_bytes, gmd_stream_t stream,
-                 const GnTail* gn) {
+                 const GnTail* gn, const void* X2 = nullptr, int K2 = 0, int64_t ldx2 = 0) {
     const bool split = gmd_is_split(dtype);
     GMD_REQUIRE(dtype == GMD_BF16 || dtype == GMD_F16 || dtype == GMD_F32 || split, "gmd_conv3x3: bad dtype %d", dtype);
     const bool is16 = gmd_is_half(dtype);
@@ -2608,15 +2679,23 @@ int conv3x3_impl(const void* X, const void* Wt, void* Y, int dtype, int out_dtyp
     GMD_REQUIRE(residual == nullptr || out_dtype == dtype || !is16, "gmd_conv3x3: residual needs out_dtype == dtype");
     const int64_t M = (int64_t)B * Hout * Wout;
     GMD_REQUIRE(M < (1LL << 31), "gmd_conv3x3: too many output pixels");
+    if (X2 || K2) {  // K tail (gmd_conv3x3_tail): K2 more channels of X2 [M, ldx2] behind the nine taps
+        GMD_REQUIRE(is16, "gmd_conv3x3_tail: the 16-bit types only (dtype %d)", dtype);
+        GMD_REQUIRE(stride == 1 && !upsample && pad_mode == 0 && !gn, "gmd_conv3x3_tail: stride 1, no upsampling, no fused GroupNorm");
+        GMD_REQUIRE(K2 > 0 && K2 % 64 == 0, "gmd_conv3x3_tail: K2=%d must be a positive multiple of 64", K2);
+        GMD_REQUIRE(X2 && gmd_aligned16(X2) && ldx2 >= K2 && ldx2 % 8 == 0, "gmd_conv3x3_tail: null or unaligned X2, or bad ldx2=%lld", (long long)ldx2);
+    }
     GemmParams p{};
-    p.A = X; p.W = Wt; p.C = Y; p.M = (int)M; p.N = Cout; p.K = 9 * Cin;
-    p.lda = Cin; p.ldw = 9 * (int64_t)Cin; p.ldc = Cout;
+    p.A = X; p.W = Wt; p.C = Y; p.M = (int)M; p.N = Cout; p.K = 9 * Cin + K2;
+    p.lda = Cin; p.ldw = 9 * (int64_t)Cin + K2; p.ldc = Cout;
     {
         const int es = is16 ? 2 : 4;
-        const int64_t ab = (int64_t)B * Hin * Win * Cin * es, wb = (int64_t)Cout * 9 * Cin * es;
-        GMD_REQUIRE(!(is16 || split) || (ab < 0xFFFF0000LL && wb < 0xFFFF0000LL), "gmd_conv3x3: tensor larger than 4 GiB");
-        p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb;
+        const int64_t ab = (int64_t)B * Hin * Win * Cin * es, wb = (int64_t)Cout * (9 * (int64_t)Cin + K2) * es;
+        const int64_t a2b = K2 ? ((M - 1) * ldx2 + K2) * es : 0;
+        GMD_REQUIRE(!(is16 || split) || (ab < 0xFFFF0000LL && wb < 0xFFFF0000LL && a2b < 0xFFFF0000LL), "gmd_conv3x3: tensor larger than 4 GiB");
+        p.a_bytes = (unsigned)ab; p.w_bytes = (unsigned)wb; p.a2_bytes = (unsigned)a2b;
     }
+    p.A2 = X2; p.K2 = K2; p.lda2 = ldx2;
     p.bias = bias; p.rowbias = rowbias; p.rows_per_group = Hout * Wout; p.ldrb = ldrb > 0 ? ldrb : Cout;
     p.residual = residual; p.ldr = Cout; p.alpha = alpha; p.act = GMD_ACT_NONE;
     p.out_f32 = out_dtype == GMD_F32;
@@ -2650,6 +2729,15 @@ int gmd_conv3x3(const void* X, const void* Wt, void* Y, int dtype, int out_dtype
                 float alpha, float* colstats, int colstats_bucket, void* workspace, int64_t workspace_bytes, gmd_stream_t stream) {
     return conv3x3_impl(X, Wt, Y, dtype, out_dtype, B, Hin, Win, Cin, Cout, stride, upsample, pad_mode, bias, rowbias, ldrb, residual, alpha,
                         colstats, colstats_bucket, workspace, gmd_ws_usable_bytes(workspace_bytes), stream, nullptr);
+}
+
+int gmd_conv3x3_tail(const void* X, const void* X2, const void* Wt, void* Y, int dtype, int out_dtype, int B, int Hin, int Win, int Cin, int K2,
+                     int64_t ldx2, int Cout, int stride, int upsample, int pad_mode, const float* bias, const float* rowbias, int64_t ldrb,
+                     const void* residual, float alpha, float* colstats, int colstats_bucket, void* workspace, int64_t workspace_bytes,
+                     gmd_stream_t stream) {
+    GMD_REQUIRE(X2 && K2 > 0, "gmd_conv3x3_tail: no second operand (X2 NULL or K2=%d)", K2);
+    return conv3x3_impl(X, Wt, Y, dtype, out_dtype, B, Hin, Win, Cin, Cout, stride, upsample, pad_mode, bias, rowbias, ldrb, residual, alpha,
+                        colstats, colstats_bucket, workspace, gmd_ws_usable_bytes(workspace_bytes), stream, nullptr, X2, K2, ldx2);
 }
 
 int gmd_conv3x3_gn_fusable(int dtype, int B, int Hin, int Win, int Cin, int Cout, int stride, int upsample, int pad_mode, int groups,

@@ -55,6 +55,13 @@ struct GemmParams {
     int fixup;
     unsigned fix_bytes;
     unsigned* fix_cnt;
+    // conv3x3 K tail (gmd_conv3x3_tail; gemm_pp_kernel<CONV> only): behind the nine taps over Cin channels of A the K loop goes on over
+    // K2 channels of a second operand A2, row-major [M, lda2] and read at the output pixel itself (a 1x1 tap): K = 9 Cin + K2, and W is
+    // ONE matrix [N, 9 Cin + K2].  K2 == 0: no tail.  a2_bytes: extent of A2 for its buffer descriptor.
+    const void* A2;
+    int K2;
+    int64_t lda2;
+    unsigned a2_bytes;
 };
 
 // The last GMD_WS_TAIL bytes of a caller's workspace hold the arrival counters of the in-kernel split-K reduction (one per tile):

@@ -153,6 +153,9 @@ class AutoencoderKL(_HipModule):
             r = dict(n1=self._norm(k + ".norm1"), c1=self._conv3(k + ".conv1"), n2=self._norm(k + ".norm2"), c2=self._conv3(k + ".conv2"))
             if k + ".conv_shortcut.weight" in self._raw:
                 r["sc"] = self._lin(k + ".conv_shortcut")
+                # conv2 + shortcut as one launch (hip_ops.conv3x3_tail), as in the UNet's resnets
+                if ops.USE_SHORTCUT_FOLD and ops.is_half(self._dtype) and r["sc"][0].shape[1] % 64 == 0:
+                    r["c2sc"] = ops.pack_shortcut(r["c2"][0], r["c2"][1], r["sc"][0], r["sc"][1])
             return r
 
         def mid(k):
@@ -214,6 +217,10 @@ class AutoencoderKL(_HipModule):
         h, _, _ = ops.conv3x3(h, r["c1"][0], B, H, W, bias=r["c1"][1])
         h = ops.groupnorm(h, B, G, r["n2"][0], r["n2"][1], 1e-6, silu=True)
         if "sc" in r:
+            if "c2sc" in r and ops.shortcut_fold_ok(self._dtype, B, H, W, h.shape[-1], x.shape[-1], r["c2sc"][0].shape[0]):
+                y, _, _ = ops.conv3x3_tail(h, x, r["c2sc"][0], B, H, W, bias=r["c2sc"][1])
+                return y
+            ops.shortcut_launches += 1
             x = ops.gemm_nt(x.view(-1, x.shape[-1]), r["sc"][0], bias=r["sc"][1]).view(B, H * W, -1)
         y, _, _ = ops.conv3x3(h, r["c2"][0], B, H, W, bias=r["c2"][1], residual=x)
         return y

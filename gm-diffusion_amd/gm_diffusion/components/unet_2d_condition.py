@@ -454,6 +454,10 @@ class UNet2DConditionModel(_HipModule):
             te_b.append(self._raw[k + ".time_emb_proj.bias"])
             if k + ".conv_shortcut.weight" in self._raw:
                 r["sc"] = self._lin(k + ".conv_shortcut")
+                # conv2 + shortcut as one launch (hip_ops.conv3x3_tail): [W2 | Wsc] packed once, the two biases summed in float32.  The
+                # separate weights stay for the shapes whose plan has no K-tail loader and for GMD_FUSE_SHORTCUT=0.
+                if ops.USE_SHORTCUT_FOLD and ops.is_half(self._dtype) and r["sc"][0].shape[1] % 64 == 0:
+                    r["c2sc"] = ops.pack_shortcut(r["c2"][0], r["c2"][1], r["sc"][0], r["sc"][1])
             return r
 
         def transformer(k, heads, depth):
@@ -548,6 +552,10 @@ class UNet2DConditionModel(_HipModule):
                                      rowbias=(temb, r["te_off"]), colstats=cs, split_out=self._sa(r["c2"][0]))
         if "sc" in r:
             cin = x.shape[-1]
+            if "c2sc" in r and ops.shortcut_fold_ok(self._dtype, B, H, W, h.shape[-1], cin, r["c2sc"][0].shape[0]):
+                y, _, _ = ops.conv3x3_tail(h, x, r["c2sc"][0], B, H, W, bias=r["c2sc"][1], colstats=cs)
+                return y
+            ops.shortcut_launches += 1
             x = ops.gemm_nt(x.view(-1, cin), r["sc"][0], bias=r["sc"][1]).view(B, H * W, -1)
         y, _, _ = ops.conv3x3(h, r["c2"][0], B, H, W, bias=r["c2"][1], residual=x, colstats=cs)
         return y

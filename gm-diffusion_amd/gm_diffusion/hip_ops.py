@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -563,6 +563,78 @@ def conv3x3(x, w, B, H, W, bias=None, rowbias=None, residual=None, stride=1, ups
     if st is not None:
         y._colstats = (st, cout)
     return y, ho, wo
+
+
+# ResnetBlock2D's conv2(h) + conv_shortcut(x) as ONE launch (gmd_conv3x3_tail): the shortcut projection is K2/64 more steps of conv2's
+# K loop over the packed weight [W2 | Wsc], summed in the float32 accumulator; its [M, Cout] tensor is never written.
+# GMD_FUSE_SHORTCUT=0 keeps the two launches (A/B measurements, tests).
+USE_SHORTCUT_FOLD = os.environ.get("GMD_FUSE_SHORTCUT", "1") != "0"
+shortcut_fold_uses = 0   # fused launches issued (tests assert the path is really taken)
+shortcut_launches = 0    # separate conv_shortcut projections issued by the models' resnets
+
+
+def pack_shortcut(w2, b2, wsc, bsc):
+    """([W2 | Wsc] as one [Cout, 9*Cin + K2] matrix, b2 + bsc in float32) for conv3x3_tail.  The weights are copied bit for bit (no
+    re-rounding); a side without a bias counts as zero."""
+    if w2.dim() != 2 or wsc.dim() != 2 or w2.shape[0] != wsc.shape[0] or w2.dtype != wsc.dtype or w2.device != wsc.device:
+        raise HipExtensionError(f"pack_shortcut: W2 {tuple(w2.shape)} {w2.dtype} and Wsc {tuple(wsc.shape)} {wsc.dtype} do not stack")
+    if getattr(w2, "_split", False) or getattr(wsc, "_split", False) or getattr(w2, "_alpha", 1.0) != 1.0 or getattr(wsc, "_alpha", 1.0) != 1.0:
+        raise HipExtensionError("pack_shortcut: plain (unscaled, unsplit) weights only")
+    w = torch.cat([w2, wsc], 1).contiguous()
+    b = None
+    if b2 is not None or bsc is not None:
+        zero = torch.zeros(w.shape[0], dtype=torch.float32, device=w.device)
+        b = ((zero if b2 is None else _f32(b2, "bias")) + (zero if bsc is None else _f32(bsc, "bias"))).contiguous()
+    return w, b
+
+
+def shortcut_fold_ok(dtype, B, H, W, cin, k2, cout):
+    """Does ``conv3x3_tail`` of these dimensions launch (16-bit, K2 a multiple of 64, and the 256-row ping-pong plan, the one kernel
+    whose loader walks the tail)?  The calling thread's plan family counts, as for the launch itself."""
+    if not USE_SHORTCUT_FOLD or not is_half(dtype) or k2 <= 0 or k2 % 64 or cin % 64:
+        return False
+    bm, bn, pf, _ = gemm_plan_info(dtype, B * H * W, cout, 9 * cin + k2)
+    return pf == 283 and bm == 256 and bn in (128, 160)
+
+
+def conv3x3_tail(x, x2, w, B, H, W, bias=None, rowbias=None, residual=None, out_dtype=None, colstats=False, ldx2=None, k2=None,
+                 stride=1, upsample=False):
+    """``conv3x3(x, w[:, :9*Cin]) + x2 @ w[:, 9*Cin:].T`` (+ bias, rowbias, residual) as one launch.  x: [B, H*W, Cin]; x2: [B, H*W, K2]
+    (or rows of ``ldx2`` >= K2 elements of which the first ``k2`` count); w: [Cout, 9*Cin + K2] from ``pack_shortcut``.  Returns
+    ([B, H*W, Cout], H, W).  Raises where ``shortcut_fold_ok`` is false (stride / upsample exist only to be refused by the library)."""
+    global shortcut_fold_uses
+    _dev(x, x2, w, bias, residual)
+    rb_ptr, rb_ld = _rowbias(rowbias)
+    cin, cout = x.shape[-1], w.shape[0]
+    ldx2 = int(ldx2 or x2.shape[-1])
+    k2 = int(k2 if k2 is not None else x2.shape[-1])
+    if (x.numel() != B * H * W * cin or x2.numel() != B * H * W * ldx2 or w.shape[1] != 9 * cin + k2 or x.dtype != w.dtype
+            or x2.dtype != w.dtype or k2 > ldx2):
+        raise HipExtensionError(f"conv3x3_tail: shape/dtype mismatch x={tuple(x.shape)} x2={tuple(x2.shape)} w={tuple(w.shape)} B,H,W={B},{H},{W}")
+    if getattr(w, "_split", False) or is_asplit(x) or is_asplit(x2):
+        raise HipExtensionError("conv3x3_tail: plain operands only")
+    out_dtype = out_dtype or x.dtype
+    y = torch.empty((B, H * W, cout), dtype=out_dtype, device=x.device)
+    if residual is not None and (residual.numel() != y.numel() or residual.dtype != x.dtype):
+        raise HipExtensionError("conv3x3_tail: residual shape/dtype mismatch")
+    if rowbias is not None and (rowbias[0] if isinstance(rowbias, tuple) else rowbias).shape[0] != B:
+        raise HipExtensionError("conv3x3_tail: rowbias must have one row per sample")
+    ws = _workspace(x.device)
+    code = dtype_code(x.dtype)
+    st = _colstats_buffer(colstats, x.dtype, B * H * W, cout, 9 * cin + k2, 1, out_dtype, x.device) if is_half(x.dtype) else None
+    tm = profiling.active()
+    tm = tm if tm is not None and tm.wants("conv3x3") else None
+    t0 = tm.begin() if tm else None
+    check(lib().gmd_conv3x3_tail(_ptr(x), _ptr(x2), _ptr(w), _ptr(y), code, dtype_code(out_dtype), B, H, W, cin, k2, ldx2, cout,
+                                 int(stride), int(bool(upsample)), 0, _ptr(_f32(bias, "bias")), rb_ptr, rb_ld, _ptr(residual), 1.0,
+                                 _ptr(st), COLSTATS_BUCKET if st is not None else 0, _ptr(ws), WORKSPACE_BYTES, _stream()), "gmd_conv3x3_tail")
+    if tm:
+        tm.end("conv3x3", 2.0 * B * H * W * cout * (9 * cin + k2), (x.numel() + x2.numel() + w.numel()) * x.element_size()
+               + y.numel() * y.element_size(), t0)
+    shortcut_fold_uses += 1
+    if st is not None:
+        y._colstats = (st, cout)
+    return y, H, W
 
 
 USE_CONV_GN_FUSION = os.environ.get("GMD_CONV_GN", "1") != "0"  # (the switch: A/B measurements only)

@@ -447,6 +447,23 @@ int gmd_conv3x3(const void* X, const void* Wt, void* Y, int dtype, int out_dtype
                 float* colstats, int colstats_bucket,
                 void* workspace, int64_t workspace_bytes, gmd_stream_t stream);
 
+/* gmd_conv3x3 with a K TAIL (added within ABI v14: one new entry point, no signature changed): behind the nine taps over the Cin
+ * channels of X the contraction goes on over K2 channels of a second operand X2, row-major [B*Hin*Win, ldx2] (ldx2 >= K2, a multiple
+ * of 8) and read at the output pixel itself -- a 1x1 tap:
+ *     Y = alpha * (conv3x3(X, Wt[:, :9 Cin]) + X2 Wt[:, 9 Cin:]^T) + bias + rowbias + residual,    Wt: ONE matrix [Cout, 9*Cin + K2].
+ * This is diffusers' ResnetBlock2D tail, conv2(h) + conv_shortcut(x), as one launch: the shortcut projection is K2/64 more steps of
+ * the K loop that already owns the output tile, summed in the float32 accumulator (the two-launch form rounds the shortcut to 16
+ * bits first), and its [M, Cout] tensor is neither written nor read back as `residual`.  The caller packs [W2 | Wsc] and adds the
+ * two biases.  16-bit dtypes, stride 1, no upsampling, pad_mode 0, K2 % 64 == 0: anything else returns GMD_ERR_INVALID before a
+ * launch, and so does a launch whose plan is not the 256-row ping-pong kernel (or its patch-resident form) (gmd_gemm_plan_info with K = 9*Cin + K2 answers
+ * {256, 160 | 128, 283, .}: ask it first and issue gmd_gemm_nt + gmd_conv3x3 otherwise).  Epilogue, column statistics, out_dtype
+ * and workspace exactly as gmd_conv3x3; split-K plans (either reduction) slice the 9*Cin/64 + K2/64 steps as one K. */
+int gmd_conv3x3_tail(const void* X, const void* X2, const void* Wt, void* Y, int dtype, int out_dtype,
+                     int B, int Hin, int Win, int Cin, int K2, int64_t ldx2, int Cout, int stride, int upsample, int pad_mode,
+                     const float* bias, const float* rowbias, int64_t ldrb, const void* residual, float alpha,
+                     float* colstats, int colstats_bucket,
+                     void* workspace, int64_t workspace_bytes, gmd_stream_t stream);
+
 /* conv3x3 whose output goes straight into a GroupNorm (+SiLU): ResnetBlock2D's conv1 -> (+ time embedding) -> norm2 -> SiLU
  * (diffusers ResnetBlock2D.forward; reached through UNet2DConditionModel at stable_diffusion_dual_unet.py:1052, 1083).  On the
  * 16x16 / 8x8 UNet levels the convolution runs split-K (float32 partial slabs in `workspace`); here the GroupNorm kernel sums
