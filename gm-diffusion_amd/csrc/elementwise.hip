@@ -1,5 +1,5 @@
-// Small HBM-bound elementwise kernels of the UNet: GEGLU gate, sinusoidal timestep embedding,
-// channel concat (skip connections) and dtype cast.  16-byte accesses throughout.
+// Small HBM-bound elementwise kernels of the UNet: GEGLU gate, sinusoidal timestep embedding (plain, and with the per-row addend of a
+// guidance-embedded UNet), channel concat (skip connections) and dtype cast.  16-byte accesses where the kernel is vectorised.
 #include "gmd_common.h"
 #include <math.h>
 
@@ -41,6 +41,30 @@ __global__ void temb_kernel(const float* __restrict__ t_dev, T* __restrict__ out
         T* o = out + (int64_t)b * dim;
         Elem<T>::st(o + (flip ? half + k : k), sn);
         Elem<T>::st(o + (flip ? k : half + k), cs);
+    }
+}
+
+// temb_kernel with a per-row addend, in diffusers' order for a guidance-embedded (time_cond_proj_dim) UNet: t_emb.to(dtype), then
+// + cond_proj(timestep_cond) in dtype.  The sinusoid is rounded to T first (the st/ld round trip), the sum is one float32 add rounded
+// to T once -- for 16-bit T that is the dtype's own add -- and contraction is off so that no multiply inside sinf/cosf fuses with it.
+template <typename T>
+__global__ void temb_add_kernel(const float* __restrict__ t_dev, const T* __restrict__ addend, T* __restrict__ out, int B, int dim,
+                                int flip, float shift) {
+#pragma clang fp contract(off)
+    GMD_WG_TRACE_SCOPE(WGK_TEMB);
+    const int half = dim / 2;
+    const float t = *t_dev;
+    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < B * half; i += gridDim.x * blockDim.x) {
+        const int b = i / half, k = i - b * half;
+        const float e = expf(-9.210340371976184f * (float)k / ((float)half - shift));
+        const float a = t * e;
+        const float sn = sinf(a), cs = cosf(a);
+        const int64_t js = (int64_t)b * dim + (flip ? half + k : k), jc = (int64_t)b * dim + (flip ? k : half + k);
+        T rs, rc;
+        Elem<T>::st(&rs, sn);
+        Elem<T>::st(&rc, cs);
+        Elem<T>::st(out + js, Elem<T>::ld(&rs) + Elem<T>::ld(addend + js));
+        Elem<T>::st(out + jc, Elem<T>::ld(&rc) + Elem<T>::ld(addend + jc));
     }
 }
 
@@ -135,6 +159,22 @@ int gmd_timestep_embedding(const float* t_dev, void* out, int dtype, int B, int 
         temb_kernel<T><<<grid, 256, 0, s>>>(t_dev, (T*)out, B, dim, flip_sin_to_cos, freq_shift);
     });
     GMD_CHECK_LAUNCH("gmd_timestep_embedding");
+    return GMD_OK;
+}
+
+int gmd_timestep_embedding_add(const float* t_dev, const void* addend, void* out, int dtype, int B, int dim, int flip_sin_to_cos,
+                               float freq_shift, gmd_stream_t stream) {
+    GMD_REQUIRE(B > 0 && dim > 0 && dim % 2 == 0, "gmd_timestep_embedding_add: bad shape B=%d dim=%d", B, dim);
+    GMD_REQUIRE(t_dev && addend && out, "gmd_timestep_embedding_add: null pointer");
+    GMD_REQUIRE(addend != out, "gmd_timestep_embedding_add: out must not alias the addend");
+    hipStream_t s = (hipStream_t)stream;
+    const int grid = (B * dim / 2 + 255) / 256;
+    GMD_REQUIRE(gmd_known_dtype(dtype), "gmd_timestep_embedding_add: bad dtype %d", dtype);
+    gmd_for_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        temb_add_kernel<T><<<grid, 256, 0, s>>>(t_dev, (const T*)addend, (T*)out, B, dim, flip_sin_to_cos, freq_shift);
+    });
+    GMD_CHECK_LAUNCH("gmd_timestep_embedding_add");
     return GMD_OK;
 }
 

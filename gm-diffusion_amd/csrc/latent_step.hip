@@ -1,5 +1,5 @@
 // Latent-side kernels of the denoising loop: CFG combine + x0 prediction + PNDM/PLMS update in one
-// pass, the guidance-rescale std reduction, and the UNet input pack / output unpack (8-channel
+// pass (and its siblings for DPM-Solver++, DDPM, DDIM, LCM, Euler and LMS), the guidance-rescale std reduction, and the UNet input pack / output unpack (8-channel
 // concat + CFG duplicate + NCHW<->channels-last + cast + channel padding).
 //
 // Built with -ffp-contract=off: float32 operations are issued in the same order as the torch
@@ -196,6 +196,43 @@ __global__ __launch_bounds__(kThreads) void ddim_step_kernel(
         float r = sqrt_a_prev * p0 + dir_coeff * pe;
         if (noise) r = r + std * noise[i];
         x_prev[i] = r;
+    }
+}
+
+// Latent-consistency (LCM) step -- diffusers' LCMScheduler.step, epsilon prediction -- fused with the CFG combine and the pipeline's
+// x0, in the operation order of its torch expressions (float32, no FMA):
+//   p0    = (x - sqrt(1-a_t) * eps) / sqrt(a_t)            predicted_original_sample [clamped to +-clip_range when clip_sample;
+//                                                          a NaN passes the clamp as it passes torch.clamp]
+//   den   = c_out * p0 + c_skip * x                        the consistency model's "denoised" (boundary-condition scalings)
+//   prev  = sqrt(a_prev) * den + sqrt(1-a_prev) * noise    every step but the last (noise == nullptr there: prev = den)
+// The noise is drawn by the HOST scheduler, as for DDPM and DDIM.  A guidance-embedded UNet runs without the CFG duplicate, but the
+// combine stays available: LCMScheduler also steps a plain UNet.
+__global__ __launch_bounds__(kThreads) void lcm_step_kernel(
+    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
+    float gs, const float* __restrict__ ratio, float gr, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range,
+    float c_skip, float c_out, float sqrt_a_prev, float sqrt_b_prev, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
+    float* __restrict__ x0, float* __restrict__ denoised) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const int64_t n = (int64_t)B * chw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float eps;
+        if (do_cfg) {
+            const float u = eps_in[i], t = eps_in[n + i];
+            eps = u + gs * (t - u);  // dual.py:1065
+            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
+                const float resc = eps * ratio[i / chw];
+                eps = gr * resc + (1.0f - gr) * eps;
+            }
+        } else {
+            eps = eps_in[i];
+        }
+        const float xt = x[i];
+        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (never clipped)
+        float p0 = (xt - sched_sqrt_1ma * eps) / sched_sqrt_a;
+        if (clip) p0 = p0 < -clip_range ? -clip_range : (p0 > clip_range ? clip_range : p0);  // torch.clamp: a NaN stays a NaN
+        const float den = c_out * p0 + c_skip * xt;
+        if (denoised) denoised[i] = den;
+        x_prev[i] = noise ? sqrt_a_prev * den + sqrt_b_prev * noise[i] : den;
     }
 }
 
@@ -459,6 +496,29 @@ int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B
         sched_sqrt_one_minus_alpha, clip_sample, clip_range, use_clipped, sqrt_alpha_prev, dir_coeff, std_dev, sqrt_alpha,
         sqrt_one_minus_alpha, x_prev, x0, pred_x0);
     GMD_CHECK_LAUNCH("gmd_ddim_step");
+    return GMD_OK;
+}
+
+int gmd_lcm_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
+                 const float* rescale_ratio, float guidance_rescale, float sched_sqrt_alpha, float sched_sqrt_one_minus_alpha,
+                 int clip_sample, float clip_range, float c_skip, float c_out, float sqrt_alpha_prev, float sqrt_beta_prev,
+                 float sqrt_alpha, float sqrt_one_minus_alpha, float* x_prev, float* x0, float* denoised, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && chw > 0, "gmd_lcm_step: bad shape B=%d chw=%lld", B, (long long)chw);
+    // every scalar the kernel multiplies by: a NaN coefficient (a negative alpha under the square root) is refused before the launch
+    const float c[6] = {sched_sqrt_alpha, sched_sqrt_one_minus_alpha, c_skip, c_out, sqrt_alpha_prev, sqrt_beta_prev};
+    const char* const names[6] = {"sched_sqrt_alpha", "sched_sqrt_one_minus_alpha", "c_skip", "c_out", "sqrt_alpha_prev", "sqrt_beta_prev"};
+    for (int k = 0; k < 6; ++k) GMD_REQUIRE(std::isfinite(c[k]), "gmd_lcm_step: %s must be finite (got %g)", names[k], (double)c[k]);
+    GMD_REQUIRE(x0 == nullptr || (std::isfinite(sqrt_alpha) && std::isfinite(sqrt_one_minus_alpha)),
+                "gmd_lcm_step: the pipeline x0 coefficients must be finite (got %g, %g)", (double)sqrt_alpha, (double)sqrt_one_minus_alpha);
+    GMD_REQUIRE(sched_sqrt_alpha != 0.0f && (x0 == nullptr || sqrt_alpha != 0.0f), "gmd_lcm_step: zero denominator");
+    GMD_REQUIRE(!clip_sample || clip_range > 0.0f, "gmd_lcm_step: clip_range must be positive");
+    if (B == 0) return GMD_OK;
+    GMD_REQUIRE(eps_in && x && x_prev, "gmd_lcm_step: null pointer");
+    lcm_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
+        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
+        sched_sqrt_one_minus_alpha, clip_sample, clip_range, c_skip, c_out, sqrt_alpha_prev, sqrt_beta_prev, sqrt_alpha,
+        sqrt_one_minus_alpha, x_prev, x0, denoised);
+    GMD_CHECK_LAUNCH("gmd_lcm_step");
     return GMD_OK;
 }
 

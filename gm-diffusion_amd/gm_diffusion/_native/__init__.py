@@ -42,6 +42,7 @@ SIGNATURES = {
     "gmd_dpm_sde_step": [P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, F, F, F, F, P, P, P, P],
     "gmd_ddpm_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, F, F, F, F, F, P, P, P],
     "gmd_ddim_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, I, F, F, F, F, F, P, P, P, P],
+    "gmd_lcm_step": [P, P, P, I, L, I, F, P, F, F, F, I, F, F, F, F, F, F, F, P, P, P, P],
     "gmd_euler_step": [P, P, P, I, L, I, F, P, F, F, F, F, P, P, P],
     "gmd_lms_step": [P, P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, P, P, P, P],
     "gmd_cfg_std_ratio": [P, I, L, F, P, P],
@@ -78,6 +79,7 @@ SIGNATURES = {
     "gmd_layernorm": [P, P, I, L, I, P, P, F, P],
     "gmd_geglu": [P, P, I, L, I, P],
     "gmd_timestep_embedding": [P, P, I, I, I, I, F, P],
+    "gmd_timestep_embedding_add": [P, P, P, I, I, I, I, F, P],
     "gmd_concat_channels": [P, I, P, I, P, I, L, P],
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
     "gmd_cast": [P, I, P, I, L, P],

@@ -9,11 +9,11 @@ from .clip_text_model import CLIPTextModel
 from .configuration import ConfigMixin, FrozenDict
 from .image_processor import StableDiffusionPipelineOutput, VaeImageProcessor, randn_tensor
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
-                         LMSDiscreteScheduler, PNDMScheduler)
+                         LCMScheduler, LMSDiscreteScheduler, PNDMScheduler)
 from .unet_2d_condition import UNet2DConditionModel
 
 __all__ = [
     "AutoencoderKL", "UNet2DConditionModel", "CLIPTextModel", "PNDMScheduler", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "EulerDiscreteScheduler",
-    "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "VaeImageProcessor",
+    "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "LCMScheduler", "VaeImageProcessor",
     "StableDiffusionPipelineOutput", "randn_tensor", "FrozenDict", "ConfigMixin",
 ]

@@ -2,7 +2,7 @@
 Schedulers for the MI355X build: ``PNDMScheduler`` (PLMS, the "50 PNDM steps" configuration of
 scripts/stage2/train_gm_unet.py:171-176), ``DDPMScheduler`` (scripts/inference/generate_hdr.py:162),
 ``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188),
-``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` /
+``LCMScheduler`` (few-step sampling of a guidance-embedded UNet), ``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` /
 ``LMSDiscreteScheduler`` (the only ones whose ``init_noise_sigma`` and ``scale_model_input`` do something).  In the reference they come from ``diffusers``; these
 classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241, 610-625, 715,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
@@ -477,6 +477,189 @@ class DDIMScheduler(_SchedulerBase):
                 variance_noise = randn_tensor(model_output.shape, generator=generator, device=dev, dtype=model_output.dtype)
             prev = prev + sd * variance_noise
         return (prev, p0) if not return_dict else DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
+
+
+@dataclass
+class LCMSchedulerOutput(_Output):
+    prev_sample: torch.Tensor
+    denoised: torch.Tensor = None
+
+
+class LCMScheduler(_SchedulerBase):
+    """Latent-consistency (LCM) multistep sampling: the few-step scheduler (2-8 steps) of a guidance-embedded UNet (config
+    ``time_cond_proj_dim``; the branch of the reference pipelines at stable_diffusion_gm.py:1028-1034), which runs without the
+    classifier-free-guidance duplicate.  Restates diffusers' ``LCMScheduler`` for epsilon prediction with ``clip_sample``;
+    v-prediction / sample prediction, thresholding and zero-SNR betas raise NotImplementedError.  Each step predicts x0, applies the
+    boundary-condition scalings (``denoised = c_out * x0 + c_skip * x``) and, at every step but the last, re-noises the result to
+    the next timestep of the schedule: n steps take n - 1 draws, as with DDPM.  ``step`` / ``fused_step`` run as ONE HIP kernel
+    (gmd_lcm_step) for float32 device tensors, as the same torch expressions (``_host_step``) otherwise."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.00085, beta_end=0.012, beta_schedule="scaled_linear", trained_betas=None,
+                     original_inference_steps=50, clip_sample=False, clip_sample_range=1.0, set_alpha_to_one=True, steps_offset=0,
+                     prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995, sample_max_value=1.0,
+                     timestep_spacing="leading", timestep_scaling=10.0, rescale_betas_zero_snr=False)
+
+    def __init__(self, **kwargs):
+        cfg = dict(self._defaults)
+        bad = [k for k in kwargs if k not in cfg]
+        if bad:
+            raise TypeError(f"LCMScheduler: unexpected arguments {bad}")
+        cfg.update(kwargs)
+        self.register_to_config(**cfg)
+        if cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["rescale_betas_zero_snr"]:
+            raise NotImplementedError("only epsilon prediction without thresholding / zero-SNR rescale is implemented")
+        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.custom_timesteps = False
+        self.timesteps = torch.from_numpy(np.arange(0, cfg["num_train_timesteps"])[::-1].copy().astype(np.int64))
+        self._ts_host = [int(v) for v in self.timesteps]
+        self._step_index = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps=None, device=None, original_inference_steps=None, timesteps=None, strength=1.0):
+        """The LCM schedule: the ``original_inference_steps`` training timesteps ``k, 2k, ... - 1`` (k = num_train_timesteps //
+        original_inference_steps; the first ``strength`` of them), reversed, then ``num_inference_steps`` of those picked at evenly
+        spaced indices.  ``timesteps=`` gives a custom strictly descending schedule instead."""
+        c = self.config
+        if num_inference_steps is None and timesteps is None:
+            raise ValueError("Must pass exactly one of `num_inference_steps` or `timesteps`.")
+        if num_inference_steps is not None and timesteps is not None:
+            raise ValueError("Can only pass one of `num_inference_steps` or `timesteps`.")
+        orig = original_inference_steps if original_inference_steps is not None else c.original_inference_steps
+        if orig > c.num_train_timesteps:
+            raise ValueError(f"`original_steps`: {orig} cannot be larger than `self.config.train_timesteps`: {c.num_train_timesteps}"
+                             " as the unet model trained with this scheduler can only handle maximal"
+                             f" {c.num_train_timesteps} timesteps.")
+        k = c.num_train_timesteps // orig
+        origin = np.arange(1, int(orig * strength) + 1) * k - 1
+        if timesteps is not None:
+            ts = np.array(timesteps, dtype=np.int64)
+            if ts.ndim != 1 or len(ts) == 0:
+                raise ValueError("`timesteps` must be a non-empty list of ints.")
+            if any(ts[i] >= ts[i - 1] for i in range(1, len(ts))):
+                raise ValueError("`timesteps` must be in descending order.")
+            if ts[0] >= c.num_train_timesteps:
+                raise ValueError(f"`timesteps` must start before `self.config.train_timesteps`: {c.num_train_timesteps}.")
+            if ts[-1] < 0:
+                raise ValueError("`timesteps` must not be negative.")
+            num_inference_steps = len(ts)
+            self.custom_timesteps = True
+        else:
+            if num_inference_steps > c.num_train_timesteps:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `self.config.train_timesteps`:"
+                                 f" {c.num_train_timesteps} as the unet model trained with this scheduler can only handle"
+                                 f" maximal {c.num_train_timesteps} timesteps.")
+            if num_inference_steps > orig:
+                raise ValueError(f"`num_inference_steps`: {num_inference_steps} cannot be larger than `original_inference_steps`: {orig}"
+                                 " because the final timestep schedule will be a subset of the `original_inference_steps`-sized"
+                                 " initial timestep schedule.")
+            skipping = len(origin) // num_inference_steps if num_inference_steps > 0 else 0
+            if skipping < 1:
+                raise ValueError(f"The combination of `original_steps x strength`: {orig} x {strength} is smaller than"
+                                 f" `num_inference_steps`: {num_inference_steps}. Make sure to either reduce `num_inference_steps` to a"
+                                 f" value smaller than {int(orig * strength)} or increase `strength` to a value higher than"
+                                 f" {float(num_inference_steps / orig)}.")
+            origin = origin[::-1].copy()
+            idx = np.floor(np.linspace(0, len(origin), num=num_inference_steps, endpoint=False)).astype(np.int64)
+            ts = origin[idx].astype(np.int64)
+            self.custom_timesteps = False
+        self.num_inference_steps = num_inference_steps
+        self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.long)
+        self._ts_host = [int(v) for v in ts]
+        self._step_index = None
+
+    def _init_step_index(self, timestep):
+        t = int(timestep)
+        idx = [k for k, v in enumerate(self._ts_host) if v == t]
+        if not idx:
+            raise ValueError(f"timestep {t} is not in the schedule {self._ts_host}")
+        self._step_index = idx[1] if len(idx) > 1 else idx[0]
+
+    def draws_noise(self, timestep):
+        """True when ``step`` at this timestep consumes the generator: every step but the schedule's last."""
+        return int(timestep) != self._ts_host[-1]
+
+    def get_scalings_for_boundary_condition_discrete(self, timestep):
+        """(c_skip, c_out) of the consistency model's boundary condition, in Python floats: sigma_data = 0.5."""
+        s = int(timestep) * self.config.timestep_scaling
+        return 0.25 / (s * s + 0.25), s / (s * s + 0.25) ** 0.5
+
+    def _plan(self, timestep):
+        """Host side of one step: (last, the step's coefficients as float32 0-d tensors) -- a_t ** 0.5, (1 - a_t) ** 0.5, c_skip,
+        c_out, a_prev ** 0.5, (1 - a_prev) ** 0.5, a_t -- with the previous timestep taken from the schedule (the timestep itself
+        at the last step).  c_skip / c_out are evaluated in Python floats and rounded to float32 once."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        t = int(timestep)
+        nxt = self._step_index + 1
+        last = nxt >= len(self._ts_host)
+        prev_t = t if last else self._ts_host[nxt]
+        a_t = self.alphas_cumprod[t]
+        a_prev = self.alphas_cumprod[prev_t] if prev_t >= 0 else self.final_alpha_cumprod
+        c_skip, c_out = self.get_scalings_for_boundary_condition_discrete(t)
+        f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+        return last, (a_t ** 0.5, (1 - a_t) ** 0.5, f32(c_skip), f32(c_out), a_prev ** 0.5, (1 - a_prev) ** 0.5, a_t)
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise=None,
+                     want_denoised=False):
+        """One HIP kernel pass (gmd_lcm_step): CFG combine (+rescale), pipeline x0, (clipped) x0 prediction, boundary scalings and
+        the re-noising.  The noise is drawn HERE with ``randn_tensor`` exactly where ``step`` draws it (every step but the last), so
+        a generator shared by the two schedulers of the dual pipeline is consumed in the reference's order.
+        Returns (prev_sample, x0 | None, denoised | None)."""
+        last, (sa, s1, cs, co, sp, bp, a_t) = self._plan(timestep)
+        if last:
+            noise = None
+        elif noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order: see fused_step)
+            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        out = ops.lcm_step(eps_in.contiguous(), sample.contiguous(),
+                           (sa.item(), s1.item(), cs.item(), co.item(), sp.item(), bp.item(), a_t.sqrt().item(), (1 - a_t).sqrt().item()),
+                           do_cfg, guidance_scale, noise=noise, ratio=ratio, guidance_rescale=guidance_rescale,
+                           clip_range=self.config.clip_sample_range if self.config.clip_sample else None,
+                           want_x0=want_x0, want_denoised=want_denoised)
+        self._step_index += 1
+        return out
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None):
+        """Same contract as ``DDPMScheduler.fused_step`` (device float32 tensors only).  ``noise``: this step's noise already drawn
+        from ``generator`` by the caller; ignored at the last step, which adds none.  Returns (prev_sample, x0 | None)."""
+        prev, x0, _ = self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise)
+        return prev, x0
+
+    def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
+        """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor: what ``generator`` would have given
+        at this step, so it may come together with the generator, which it leaves untouched."""
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, _, den = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, noise, want_denoised=True)
+            return (prev, den) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=den)
+        return self._host_step(model_output, timestep, sample, generator, return_dict, noise)
+
+    def _host_step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
+        """The torch expressions of diffusers' ``LCMScheduler.step`` (host tensors; also the reference for the kernel test)."""
+        dev = model_output.device
+        last, coefs = self._plan(timestep)
+        sa, s1, cs, co, sp, bp, _ = (c.to(dev) for c in coefs)
+        p0 = (sample - s1 * model_output) / sa
+        if self.config.clip_sample:
+            p0 = p0.clamp(-self.config.clip_sample_range, self.config.clip_sample_range)
+        denoised = co * p0 + cs * sample
+        if last:
+            prev = denoised
+        else:
+            if noise is None:
+                noise = randn_tensor(model_output.shape, generator=generator, device=dev, dtype=denoised.dtype)
+            prev = sp * denoised + bp * noise
+        self._step_index += 1
+        return (prev, denoised) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=denoised)
 
 
 class DPMSolverMultistepScheduler(_SchedulerBase):

@@ -260,8 +260,11 @@ class UNet2DConditionModel(_HipModule):
             cfg["attention_head_dim"] = config["num_attention_heads"]
         if isinstance(cfg["attention_head_dim"], (list, tuple)) and len(set(cfg["attention_head_dim"])) == 1:
             cfg["attention_head_dim"] = cfg["attention_head_dim"][0]
-        if cfg["act_fn"] != "silu" or cfg["time_cond_proj_dim"] is not None or cfg["center_input_sample"]:
-            raise NotImplementedError("only silu / no time_cond_proj / no centering UNets are implemented (SD-1.5, SDXL)")
+        if cfg["act_fn"] != "silu" or cfg["center_input_sample"]:
+            raise NotImplementedError("only silu / no centering UNets are implemented (SD-1.5, SDXL, guidance-embedded LCM)")
+        tcd = cfg["time_cond_proj_dim"]
+        if tcd is not None and (isinstance(tcd, bool) or not isinstance(tcd, int) or tcd <= 0):
+            raise ValueError(f"time_cond_proj_dim must be a positive int or None (got {tcd!r})")
         if cfg["addition_embed_type"] not in (None, "text_time"):
             raise NotImplementedError(f"addition_embed_type={cfg['addition_embed_type']!r}")
         self._unknown_config = unknown
@@ -273,6 +276,7 @@ class UNet2DConditionModel(_HipModule):
         self._transformers = []
         self._graphs = {}
         self._aug = {}  # text_time conditioning: persistent [B, temb] buffers, rewritten in place by set_added_cond
+        self._tcond = {}  # time_cond_proj_dim: persistent [B, ch0] buffers of cond_proj(timestep_cond), rewritten in place by set_timestep_cond
 
     # ------------------------------------------------------------------------------------------
     # structure
@@ -349,6 +353,8 @@ class UNet2DConditionModel(_HipModule):
 
         conv("conv_in", ch[0], c.in_channels, 3)
         lin("time_embedding.linear_1", temb, ch[0]); lin("time_embedding.linear_2", temb, temb)
+        if c.time_cond_proj_dim is not None:  # guidance-embedded (LCM) UNets: diffusers TimestepEmbedding.cond_proj, no bias
+            lin("time_embedding.cond_proj", ch[0], c.time_cond_proj_dim, False)
         if c.addition_embed_type == "text_time":
             lin("add_embedding.linear_1", temb, c.projection_class_embeddings_input_dim); lin("add_embedding.linear_2", temb, temb)
         downs, ups = self._layout()
@@ -443,6 +449,12 @@ class UNet2DConditionModel(_HipModule):
         w["conv_in"] = self._conv3("conv_in", self._cin_pad)
         w["te1"] = self._lin("time_embedding.linear_1")
         w["te2"] = self._lin("time_embedding.linear_2")
+        if c.time_cond_proj_dim is not None:
+            wc = self._raw["time_embedding.cond_proj.weight"]  # K = time_cond_proj_dim: zero-padded to the kernels' K multiple
+            self._tcond_k = _pad_to(wc.shape[1], self._kmul())
+            wp = torch.zeros(wc.shape[0], self._tcond_k)
+            wp[:, : wc.shape[1]] = wc
+            w["cond_proj"] = self._wt(wp)
 
         te_w, te_b = [], []
         self._transformers = []
@@ -531,6 +543,7 @@ class UNet2DConditionModel(_HipModule):
         self._kv_cache = {}
         self._graphs = {}
         self._aug = {}
+        self._tcond = {}
         self._t_dev = torch.zeros(1, dtype=torch.float32, device=self._device)
         return w
 
@@ -698,7 +711,8 @@ class UNet2DConditionModel(_HipModule):
     def supports_cfg_shared(self):
         """True when the first down block has a transformer (SD-1.5): the prefix shared by a CFG pair ends at its
         cross-attention."""
-        return self.config.down_block_types[0].startswith("CrossAttn") and self.config.addition_embed_type is None
+        c = self.config  # (a per-row conditioning of the time embedding may differ between the two halves: no shared prefix then)
+        return c.down_block_types[0].startswith("CrossAttn") and c.addition_embed_type is None and c.time_cond_proj_dim is None
 
     @_in_own_f32_mode
     def set_added_cond(self, added_cond_kwargs, B):
@@ -747,6 +761,61 @@ class UNet2DConditionModel(_HipModule):
         ent["src"] = (te, ids)  # keep the sources alive while the key is valid
         return ent["aug"]
 
+    def _tcond_entry(self, B):
+        """The persistent [B, ch0] buffer of ``cond_proj(timestep_cond)`` for batch ``B``; created as zeros (diffusers'
+        ``timestep_cond=None``) on first use, never inside a graph capture."""
+        ent = self._tcond.get(B)
+        if ent is None:
+            if self._capturing:
+                raise HipExtensionError("the timestep conditioning must be prepared (set_timestep_cond) before graph capture")
+            buf = torch.zeros((B, self.config.block_out_channels[0]), dtype=self._dtype, device=self._device)
+            ent = self._tcond[B] = dict(buf=buf, key=None, src=None)
+        return ent
+
+    @_in_own_f32_mode
+    def set_timestep_cond(self, cond, B):
+        """Guidance-scale conditioning of a guidance-embedded (LCM) UNet (diffusers ``TimestepEmbedding.cond_proj``, config
+        ``time_cond_proj_dim``): ``cond`` [B, time_cond_proj_dim] (the pipelines' ``get_guidance_scale_embedding``) goes through the
+        bias-free projection once (eager, HIP GEMM) into a persistent [B, block_out_channels[0]] buffer in the UNet dtype, which
+        every forward adds to the sinusoidal embedding in front of ``time_embedding.linear_1``.  None zeroes the buffer (diffusers'
+        ``timestep_cond=None``).  Constant over the denoising loop; a captured graph keeps reading the buffer, rewritten in place
+        here, so one capture serves every guidance scale."""
+        self._ensure()
+        d = self.config.time_cond_proj_dim
+        if d is None:
+            if cond is not None:
+                raise ValueError("this UNet has no time_embedding.cond_proj (config time_cond_proj_dim is None): timestep_cond given")
+            return None
+        if cond is None:
+            ent = self._tcond_entry(B)
+            if ent["key"] is not None:
+                if self._capturing:
+                    raise HipExtensionError("the timestep conditioning must be prepared (set_timestep_cond) before graph capture")
+                ent["buf"].zero_()
+                ent["key"] = ent["src"] = None
+            return ent["buf"]
+        if cond.dim() != 2 or tuple(cond.shape) != (B, d) or not cond.is_cuda:
+            raise ValueError(f"timestep_cond must be a device tensor of shape [{B}, {d}] (time_cond_proj_dim); got {tuple(cond.shape)}"
+                             f" on {cond.device}")
+        key = (cond.data_ptr(), cond._version, B)
+        ent = self._tcond.get(B)
+        if ent is not None and ent["key"] == key:
+            return ent["buf"]
+        if self._capturing:
+            raise HipExtensionError("the timestep conditioning must be prepared (set_timestep_cond) before graph capture")
+        ent = self._tcond_entry(B)
+        src = cond.contiguous()
+        if src.dtype != self._dtype:
+            src = ops.cast(src if src.dtype in (torch.float32, torch.bfloat16, torch.float16) else src.float(), self._dtype)
+        if self._tcond_k != d:
+            pad = torch.zeros((B, self._tcond_k), dtype=self._dtype, device=self._device)
+            pad[:, :d].copy_(src)
+            src = pad
+        ent["buf"].copy_(ops.gemm_nt(src, self._w["cond_proj"]))  # in place: a captured graph keeps reading this buffer
+        ent["key"] = key
+        ent["src"] = cond  # keep the source alive while the key is valid
+        return ent["buf"]
+
     @_in_own_f32_mode
     def forward_packed(self, x, B, H, W, encoder_hidden_states, cfg_shared=False):
         """x: packed channels-last input [B, H*W, cin_pad]; the timestep must already be in ``_t_dev``.
@@ -777,7 +846,11 @@ class UNet2DConditionModel(_HipModule):
             raise HipExtensionError("encoder_hidden_states must already be in the UNet dtype (use prepare_context)")
         if cfg_shared and (B % 2 or not self.supports_cfg_shared()):
             raise HipExtensionError("cfg_shared needs an even batch and a transformer in the first down block")
-        te = ops.timestep_embedding(self._t_dev, B, c.block_out_channels[0], self._dtype, c.flip_sin_to_cos, c.freq_shift)
+        if c.time_cond_proj_dim is None:
+            te = ops.timestep_embedding(self._t_dev, B, c.block_out_channels[0], self._dtype, c.flip_sin_to_cos, c.freq_shift)
+        else:  # t_emb.to(dtype) + cond_proj(timestep_cond) in ONE launch, as the plain embedding; zeros until set_timestep_cond
+            te = ops.timestep_embedding_add(self._t_dev, self._tcond_entry(B)["buf"], B, c.block_out_channels[0], self._dtype,
+                                            c.flip_sin_to_cos, c.freq_shift)
         te = ops.gemm_nt(te, w["te1"][0], bias=w["te1"][1], act=ops.ACT_SILU)
         aug = None
         if c.addition_embed_type == "text_time":  # emb = time_embedding(t) + add_embedding(...): the sum goes through the SiLU below
@@ -841,6 +914,8 @@ class UNet2DConditionModel(_HipModule):
         self.update_context(ehs)
         if self.config.addition_embed_type is not None and B not in self._aug:
             raise HipExtensionError("set_added_cond(added_cond_kwargs, batch) must precede graphed_forward for this UNet")
+        if self.config.time_cond_proj_dim is not None:
+            self._tcond_entry(B)  # exists (zeros unless set_timestep_cond wrote it) before the capture reads it
         key = (B, H, W, tuple(ehs.shape), bool(cfg_shared), bool(co_run))
         g = self._graphs.get(key)
         if g is not None:
@@ -909,8 +984,9 @@ class UNet2DConditionModel(_HipModule):
     @_in_own_f32_mode
     def __call__(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None, cross_attention_kwargs=None,
                  added_cond_kwargs=None, return_dict=True, **kwargs):
-        if timestep_cond is not None:
-            raise NotImplementedError("timestep_cond is not part of the GM-Diffusion path")
+        if timestep_cond is not None and self.config.time_cond_proj_dim is None:
+            raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj: its config key "
+                             "time_cond_proj_dim is None")
         self._ensure()
         first = sample[0] if isinstance(sample, (tuple, list)) else sample
         B, _, H, W = first.shape
@@ -920,6 +996,8 @@ class UNet2DConditionModel(_HipModule):
             raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != sample batch {B}")
         self.set_timestep(timestep)
         self.set_added_cond(added_cond_kwargs, B)
+        if self.config.time_cond_proj_dim is not None:
+            self.set_timestep_cond(None if timestep_cond is None else timestep_cond.to(self._device), B)
         out = self.forward_packed(x, B, H, W, ehs)
         if not return_dict:
             return (out,)

@@ -23,8 +23,8 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
-    "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
 ]
@@ -864,6 +864,20 @@ def timestep_embedding(t_dev, B, dim, dtype, flip_sin_to_cos=True, freq_shift=0.
     return out
 
 
+def timestep_embedding_add(t_dev, addend, B, dim, dtype, flip_sin_to_cos=True, freq_shift=0.0):
+    """``timestep_embedding`` plus a per-row addend [B, dim] of ``dtype``, each rounded as diffusers rounds it: the sinusoid to
+    ``dtype``, then the sum to ``dtype`` (``t_emb.to(dtype) + cond_proj(timestep_cond)``).  One launch, like the plain embedding."""
+    _dev(t_dev, addend)
+    _f32(t_dev, "timestep")
+    if addend.dtype != dtype or tuple(addend.shape) != (B, dim) or not addend.is_contiguous():
+        raise HipExtensionError(f"timestep_embedding_add: the addend must be a contiguous [{B}, {dim}] tensor of {dtype} "
+                                f"(got {tuple(addend.shape)} of {addend.dtype})")
+    out = torch.empty((B, dim), dtype=dtype, device=t_dev.device)
+    check(lib().gmd_timestep_embedding_add(_ptr(t_dev), _ptr(addend), _ptr(out), dtype_code(dtype), B, dim, int(flip_sin_to_cos),
+                                           float(freq_shift), _stream()), "gmd_timestep_embedding_add")
+    return out
+
+
 def concat_channels(a, b):
     _dev(a, b)
     ca, cb = a.shape[-1], b.shape[-1]
@@ -1164,6 +1178,30 @@ def ddim_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, 
                               float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), int(bool(use_clipped)),
                               sp, dc, sd, pa, p1, _ptr(x_prev), _ptr(x0), _ptr(pred_x0), _stream()), "gmd_ddim_step")
     return x_prev, x0, pred_x0
+
+
+def lcm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, clip_range=None,
+             want_x0=False, want_denoised=False):
+    """Fused CFG + x0 + latent-consistency (LCM) update.  coefs = (sched_sqrt_alpha, sched_sqrt_one_minus_alpha, c_skip, c_out,
+    sqrt_alpha_prev, sqrt_beta_prev, sqrt_alpha, sqrt_one_minus_alpha); ``noise`` is None at the last step, where x_prev is the
+    denoised sample itself; ``clip_range`` None = no clip_sample.  Returns (x_prev, x0|None, denoised|None): x0 is the pipeline's
+    never-clipped prediction, denoised = c_out * p0 + c_skip * x.  The outputs are allocated here, so nothing the scheduler keeps
+    is ever the static buffer of a captured graph."""
+    _dev(eps_in, x, noise, ratio)
+    for t in (eps_in, x, noise):
+        _f32(t, "latent tensors")
+    if noise is not None and noise.shape != x.shape:
+        raise HipExtensionError("lcm_step: noise must have the sample's shape")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    x_prev = torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    denoised = torch.empty_like(x) if want_denoised else None
+    sa, s1, cs, co, sp, bp, pa, p1 = (float(v) for v in coefs)
+    check(lib().gmd_lcm_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
+                             float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), cs, co, sp, bp,
+                             pa, p1, _ptr(x_prev), _ptr(x0), _ptr(denoised), _stream()), "gmd_lcm_step")
+    return x_prev, x0, denoised
 
 
 def euler_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, want_pred_x0=False):

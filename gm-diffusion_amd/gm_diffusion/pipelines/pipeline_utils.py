@@ -15,7 +15,7 @@ import os
 import torch
 
 from ..components import (AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                          EulerDiscreteScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
+                          EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
 from ..components.configuration import FrozenDict
 
 _LOADABLE = {
@@ -29,6 +29,7 @@ _LOADABLE = {
     "EulerDiscreteScheduler": EulerDiscreteScheduler,  # what an SDXL-base checkpoint's scheduler/ folder names
     "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
     "LMSDiscreteScheduler": LMSDiscreteScheduler,
+    "LCMScheduler": LCMScheduler,  # what a latent-consistency checkpoint's scheduler/ folder names
 }
 
 

@@ -50,6 +50,11 @@ the behaviour by the mathematics: the SDR UNet input is ``latents / (sigma**2 + 
 ``pred_original_sample`` ``x - sigma * eps`` (the VP expression of :1075 in exact arithmetic); the GM UNet input is
 ``cat([x0_latent, gm_latents / (sigma**2 + 1) ** 0.5])`` with x0 undivided; neither state is ever scaled.  Fused device path only: the
 generic loop raises a ValueError for such a scheduler.
+
+Guidance-embedded (LCM) UNets (config ``time_cond_proj_dim``; :1024-1030): the SDR UNet takes the embedding of ``guidance_scale - 1``
+as ``timestep_cond`` and runs without the CFG duplicate.  The reference hands that one tensor, of the SDR UNet's width, to BOTH UNets
+(:1056, :1088), which only works when both have the same ``time_cond_proj_dim``.  Here the GM UNet gets an embedding of its own
+width if and only if it has ``time_cond_proj_dim`` itself, and none otherwise: equal to the reference where the reference runs.
 """
 from __future__ import annotations
 
@@ -168,6 +173,11 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                                        self._latent_dtype(prompt_embeds, device), device, generator, latents)
         gm_latents = latents.clone()  # dual.py:1012: both streams start from the same (scaled) noise
         extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)
+        # dual.py:1024-1030: the guidance-scale embedding of a guidance-embedded (LCM) UNet, each UNet at its own width (see the module
+        # docstring); do_classifier_free_guidance is False for such an SDR UNet
+        rows = batch_size * num_images_per_prompt
+        timestep_cond = self._timestep_cond_for(self.unet, rows, device, latents.dtype)
+        gm_timestep_cond = self._timestep_cond_for(self.gm_unet, rows, device, latents.dtype)
 
         num_warmup_steps = len(timesteps) - num_inference_steps * self.scheduler.order
         self._num_timesteps = len(timesteps)
@@ -182,6 +192,8 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             # constant over the loop: written once into the persistent buffers the (captured) forwards read
             self.unet.set_added_cond(sdr_added, (2 if do_cfg else 1) * latents.shape[0])
             self.gm_unet.set_added_cond(gm_added, latents.shape[0])
+            self.unet.set_timestep_cond(timestep_cond, (2 if do_cfg else 1) * latents.shape[0])
+            self.gm_unet.set_timestep_cond(gm_timestep_cond, latents.shape[0])
             # The GM UNet of step i needs only x0_i; the SDR UNet of step i+1 needs only latents_{i+1}: the two are
             # independent, so the GM stream runs on its own HIP stream one step behind the SDR stream and their
             # kernels overlap (the batch-B GM kernels alone cannot fill 256 CUs).
@@ -250,7 +262,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
                     latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
                     gm_latents = self.gm_scheduler.scale_model_input(gm_latents, t)
-                    sdr_noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=prompt_embeds, timestep_cond=None,
+                    sdr_noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=prompt_embeds, timestep_cond=timestep_cond,
                                                cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=sdr_added,
                                                return_dict=False)[0]
                     if do_cfg:
@@ -265,7 +277,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     x0_latent = (latents - sqrt_one_minus_alpha_cumprod * sdr_noise_pred) / sqrt_alpha_cumprod
                     latents = self.scheduler.step(sdr_noise_pred, t, latents, **extra_step_kwargs, return_dict=False)[0]
                     gm_latent_input = torch.cat([x0_latent, gm_latents], dim=1)
-                    gm_noise_pred = self.gm_unet(gm_latent_input, t, encoder_hidden_states=gm_prompt_embeds, timestep_cond=None,
+                    gm_noise_pred = self.gm_unet(gm_latent_input, t, encoder_hidden_states=gm_prompt_embeds, timestep_cond=gm_timestep_cond,
                                                  cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=gm_added,
                                                  return_dict=False)[0]
                     gm_latents = self.gm_scheduler.step(gm_noise_pred, t, gm_latents, **extra_step_kwargs, return_dict=False)[0]

@@ -29,6 +29,8 @@ the reference; what runs underneath is the MI355X path:
   * with a ``PNDMScheduler`` and device tensors the per-step glue -- CFG combine, guidance
     rescale, PLMS update (:1062-1071) -- is ONE fused HIP kernel (``gmd_latent_step``) and the
     8-channel concat + CFG duplicate (:1045-1047) is folded into the UNet input pack kernel;
+  * a guidance-embedded (LCM) UNet (config ``time_cond_proj_dim``) gets the guidance-scale embedding of :1028-1034 as
+    ``timestep_cond`` and runs without the CFG duplicate; with ``LCMScheduler`` a step is ONE fused HIP kernel (``gmd_lcm_step``);
   * any other scheduler, or host tensors with a duck-typed UNet, takes the generic protocol path
     that executes the reference's torch expressions verbatim.
 
@@ -283,6 +285,32 @@ class _GMPipelineBase(DiffusionPipeline):
         latents = latents * self.scheduler.init_noise_sigma
         return latents
 
+    def get_guidance_scale_embedding(self, w: torch.Tensor, embedding_dim: int = 512, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+        """stable_diffusion_gm.py:719-747: the sinusoidal embedding of the guidance scale that a guidance-embedded (LCM) UNet takes
+        as ``timestep_cond``.  ``w``: 1-D tensor of ``guidance_scale - 1`` values.  Returns [len(w), embedding_dim] of ``dtype``:
+        ``[sin | cos]`` of ``1000 * w * exp(-ln(10000) * i / (half - 1))``, i < half = embedding_dim // 2, with one zero column
+        behind them when ``embedding_dim`` is odd."""
+        if w.dim() != 1:
+            raise ValueError(f"get_guidance_scale_embedding: `w` must be 1-D (got shape {tuple(w.shape)})")
+        half = embedding_dim // 2
+        scaled = w * 1000.0
+        decay = torch.log(torch.tensor(10000.0)) / (half - 1)
+        freqs = torch.exp(torch.arange(half, dtype=dtype) * -decay)
+        angles = scaled.to(dtype)[:, None] * freqs[None, :]
+        emb = torch.cat([angles.sin(), angles.cos()], dim=1)
+        if embedding_dim % 2 == 1:
+            emb = torch.nn.functional.pad(emb, (0, 1))
+        return emb
+
+    def _timestep_cond_for(self, unet, rows, device, dtype):
+        """stable_diffusion_gm.py:1028-1034: the ``timestep_cond`` of ``unet`` -- the embedding of ``guidance_scale - 1``, one row
+        per sample, at the UNet's own ``time_cond_proj_dim`` -- or None for a UNet without that projection."""
+        dim = getattr(unet.config, "time_cond_proj_dim", None)
+        if dim is None:
+            return None
+        w = torch.tensor(self.guidance_scale - 1).repeat(rows)
+        return self.get_guidance_scale_embedding(w, embedding_dim=dim).to(device=device, dtype=dtype)
+
     # ---- properties (stable_diffusion_gm.py:749-778) ---------------------------------------------
     @property
     def guidance_scale(self):
@@ -343,9 +371,9 @@ class _GMPipelineBase(DiffusionPipeline):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
         from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                                             EulerDiscreteScheduler, LMSDiscreteScheduler)
+                                             EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler)
 
-        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler,
+        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler, LCMScheduler,
                                                             EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler))
                 and isinstance(unet, UNet2DConditionModel))
 
@@ -371,12 +399,14 @@ class _GMPipelineBase(DiffusionPipeline):
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
         DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.  So does a
         ``DPMSolverMultistepScheduler`` with the SDE algorithm, and ``EulerAncestralDiscreteScheduler`` always; a deterministic
-        scheduler (``EulerDiscreteScheduler`` and ``LMSDiscreteScheduler`` among them) has nothing to pre-draw.
+        scheduler (``EulerDiscreteScheduler`` and ``LMSDiscreteScheduler`` among them) has nothing to pre-draw.  ``LCMScheduler`` draws
+        at every step but the last, as DDPM does.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
-        from ..components.schedulers import DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler
+        from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+                                             LCMScheduler)
 
-        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler, EulerAncestralDiscreteScheduler))
+        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler, EulerAncestralDiscreteScheduler, LCMScheduler))
                                  or (isinstance(s_, DPMSolverMultistepScheduler) and s_.draws_noise(None)))
         if generator is None or not all(takes_part(s_) for s_ in schedulers):
             return None
@@ -495,6 +525,8 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
         latents = self.prepare_latents(batch_size * num_images_per_prompt, num_channels_latents, sdr_latent.shape[-2] * 8,
                                        sdr_latent.shape[-1] * 8, self._latent_dtype(prompt_embeds, device), device, generator, latents)
         extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)
+        # gm.py:1028-1034: the guidance scale goes INTO a guidance-embedded (LCM) UNet, which then runs without the CFG duplicate
+        timestep_cond = self._timestep_cond_for(self.unet, batch_size * num_images_per_prompt, device, latents.dtype)
 
         num_warmup_steps = len(timesteps) - num_inference_steps * self.scheduler.order
         self._num_timesteps = len(timesteps)
@@ -502,6 +534,8 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
         fused = self._use_fused(latents, self.unet, self.scheduler)
         if fused:
             ctx = self.unet.prepare_context(prompt_embeds)
+            # constant over the loop: written once into the persistent buffer the (captured) forward reads
+            self.unet.set_timestep_cond(timestep_cond, (2 if do_cfg else 1) * latents.shape[0])
             sdr_f32 = sdr_latent.to(device=latents.device, dtype=torch.float32).contiguous()
             # host copy: no device sync inside the loop; int64 timesteps stay ints, the float32 (possibly fractional) timesteps of
             # a sigma-space scheduler stay floats -- never truncated
@@ -533,7 +567,7 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
                     cat_latents = torch.cat([sdr_latent, latents], dim=1)
                     latent_model_input = torch.cat([cat_latents] * 2) if do_cfg else cat_latents
                     latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
-                    noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=prompt_embeds, timestep_cond=None,
+                    noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=prompt_embeds, timestep_cond=timestep_cond,
                                            cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=None,
                                            return_dict=False)[0]
                     if do_cfg:

@@ -242,6 +242,25 @@ int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B
                   float sqrt_alpha, float sqrt_one_minus_alpha,
                   float* x_prev, float* x0, float* pred_x0, gmd_stream_t stream);
 
+/* Latent-consistency (LCM) step -- diffusers' LCMScheduler.step (epsilon prediction), the few-step sampler of a guidance-embedded
+ * UNet (time_cond_proj_dim; stable_diffusion_gm.py:1024-1030, stable_diffusion_dual_unet.py:1024-1030) -- fused with the same CFG
+ * combine / rescale and pipeline x0 as gmd_latent_step, in the float32 operation order of its torch expressions.  Added within
+ * ABI v14 (purely additive: no existing signature changed).
+ *   p0 = (x - sched_sqrt_one_minus_alpha*eps)/sched_sqrt_alpha [clamp +-clip_range]          predicted_original_sample
+ *   denoised = c_out*p0 + c_skip*x                                                           boundary-condition scalings
+ *   x_prev = noise != NULL ? sqrt_alpha_prev*denoised + sqrt_beta_prev*noise : denoised      noise == NULL at the last step
+ * c_skip = sigma_data^2/(s^2 + sigma_data^2), c_out = s/(s^2 + sigma_data^2)^0.5 with s = t*timestep_scaling, sigma_data = 0.5,
+ * sqrt_alpha_prev = a_prev ** 0.5, sqrt_beta_prev = (1 - a_prev) ** 0.5: float32 scalars computed by the host.  The noise is drawn
+ * by the host scheduler from the caller's generator, in the reference's order (SDR first, GM second).  x0 (the pipeline's, never
+ * clipped) and denoised may be NULL; nothing else is stored.  Refused before any launch: a non-finite coefficient (a NaN is
+ * refused), a zero denominator, a clip_range <= 0 with clip_sample. */
+int gmd_lcm_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw,
+                 int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                 float sched_sqrt_alpha, float sched_sqrt_one_minus_alpha, int clip_sample, float clip_range,
+                 float c_skip, float c_out, float sqrt_alpha_prev, float sqrt_beta_prev,
+                 float sqrt_alpha, float sqrt_one_minus_alpha,
+                 float* x_prev, float* x0, float* denoised, gmd_stream_t stream);
+
 /* Euler / Euler-ancestral step (diffusers' EulerDiscreteScheduler and EulerAncestralDiscreteScheduler, epsilon prediction, no
  * churn) fused with the same CFG combine / rescale as gmd_latent_step, in the float32 operation order of their torch expressions:
  *   p0 = x - sigma_hat*eps;  d = (x - p0)/sigma_hat;  x_prev = x + d*dt [ + noise*sigma_up when noise != NULL (ancestral) ]
@@ -539,6 +558,11 @@ int gmd_geglu(const void* X, void* Y, int dtype, int64_t rows, int F, gmd_stream
  * timestep read from DEVICE memory (t_dev, float32 scalar) so captured graphs can be replayed. */
 int gmd_timestep_embedding(const float* t_dev, void* out, int dtype, int B, int dim,
                            int flip_sin_to_cos, float freq_shift, gmd_stream_t stream);
+/* gmd_timestep_embedding plus a per-row addend [B, dim] of `dtype` (added within ABI v14): the time embedding input of a
+ * guidance-embedded UNet (diffusers' time_embedding.cond_proj: t_emb.to(dtype) + cond_proj(timestep_cond), then linear_1):
+ *   out[b, j] = round_dtype( float(round_dtype(sinusoid[b, j])) + float(addend[b, j]) ).  out must not alias addend. */
+int gmd_timestep_embedding_add(const float* t_dev, const void* addend, void* out, int dtype, int B, int dim,
+                               int flip_sin_to_cos, float freq_shift, gmd_stream_t stream);
 /* out[r, :Ca] = A[r], out[r, Ca:] = Bm[r]  (skip-connection concat, channels-last) */
 int gmd_concat_channels(const void* A, int Ca, const void* Bm, int Cb, void* out, int dtype,
                         int64_t rows, gmd_stream_t stream);
