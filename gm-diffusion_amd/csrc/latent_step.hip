@@ -1,5 +1,5 @@
 // Latent-side kernels of the denoising loop: CFG combine + x0 prediction + PNDM/PLMS update in one
-// pass (and its siblings for DPM-Solver++, DDPM, DDIM, LCM, Euler and LMS), the guidance-rescale std reduction, and the UNet input pack / output unpack (8-channel
+// pass (and its siblings for DPM-Solver++, DDPM, DDIM, LCM, Euler, LMS and UniPC), the guidance-rescale std reduction, and the UNet input pack / output unpack (8-channel
 // concat + CFG duplicate + NCHW<->channels-last + cast + channel padding).
 //
 // Built with -ffp-contract=off: float32 operations are issued in the same order as the torch
@@ -313,6 +313,67 @@ __global__ __launch_bounds__(kThreads) void lms_step_kernel(
     }
 }
 
+// UniPC predictor-corrector step (Zhao et al. 2023; diffusers' UniPCMultistepScheduler: predict_x0, epsilon prediction, bh1 / bh2,
+// orders 1-3) fused with the CFG combine and both x0 forms, in the operation order of the scheduler's torch expressions (float32, no FMA
+// contraction).  h1, h2, h3 are the x0 predictions of the previous 1, 2, 3 steps (m0_out of those launches), `last` the x_corr of the
+// previous launch:
+//   m0     = (x - sigma_s * eps) / alpha_s                          the x0 prediction, from x as it comes in (before the correction)
+//   corrector of order p (0 = off: x_corr = x), r_p = 1 so its D is m0 - h1:
+//     acc    = c_rho[0] * ((h2 - h1) / c_r1) [+ c_rho[1] * ((h3 - h1) / c_r2)] + c_rho[p-1] * (m0 - h1)     (p = 1: the last term alone)
+//     x_corr = c_x * last - c_m * h1 - c_b * acc
+//   predictor of order q:
+//     x_prev = p_x * x_corr - p_m * m0 [- p_b * (p_rho[0] * ((h1 - m0) / p_r1) [+ p_rho[1] * ((h2 - m0) / p_r2)])]    (q = 1: no p_b term)
+// with c_x / p_x = sigma_t/sigma_s, c_m / p_m = alpha_t*phi_1, c_b / p_b = alpha_t*B_h of the two intervals and rho = R^-1 b, all computed
+// by the host in float32.  The kernel divides by r_k, as the host expression does.  A pointer or scalar beyond the orders is never read.
+__global__ __launch_bounds__(kThreads) void unipc_step_kernel(
+    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ last, const float* __restrict__ h1,
+    const float* __restrict__ h2, const float* __restrict__ h3, int B, int64_t chw, int do_cfg, float gs, const float* __restrict__ ratio,
+    float gr, int corr_order, int pred_order, float sigma_s, float alpha_s, float c_x, float c_m, float c_b, float c_rho1, float c_rho2,
+    float c_rho3, float c_r1, float c_r2, float p_x, float p_m, float p_b, float p_rho1, float p_rho2, float p_r1, float p_r2,
+    float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out, float* __restrict__ x_corr, float* __restrict__ x_prev,
+    float* __restrict__ x0) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const int64_t n = (int64_t)B * chw;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        float eps;
+        if (do_cfg) {
+            const float u = eps_in[i], t = eps_in[n + i];
+            eps = u + gs * (t - u);  // dual.py:1065
+            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
+                const float resc = eps * ratio[i / chw];
+                eps = gr * resc + (1.0f - gr) * eps;
+            }
+        } else {
+            eps = eps_in[i];
+        }
+        const float xt = x[i];
+        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (the pipeline's own x0, from alphas_cumprod[t])
+        const float m0 = (xt - sigma_s * eps) / alpha_s;
+        m0_out[i] = m0;
+        float xc = xt;
+        if (corr_order >= 1) {
+            const float m1 = h1[i];
+            float acc;
+            if (corr_order == 1) {
+                acc = c_rho1 * (m0 - m1);
+            } else {
+                acc = c_rho1 * ((h2[i] - m1) / c_r1);
+                if (corr_order == 3) acc = acc + c_rho2 * ((h3[i] - m1) / c_r2);
+                acc = acc + (corr_order == 3 ? c_rho3 : c_rho2) * (m0 - m1);
+            }
+            xc = c_x * last[i] - c_m * m1 - c_b * acc;
+        }
+        x_corr[i] = xc;
+        float r = p_x * xc - p_m * m0;
+        if (pred_order >= 2) {
+            float acc = p_rho1 * ((h1[i] - m0) / p_r1);
+            if (pred_order == 3) acc = acc + p_rho2 * ((h2[i] - m0) / p_r2);
+            r = r - p_b * acc;
+        }
+        x_prev[i] = r;
+    }
+}
+
 // one block per sample: unbiased std over chw of text eps and of the guided eps
 __global__ __launch_bounds__(kThreads) void cfg_std_ratio_kernel(const float* __restrict__ eps_in, int B, int64_t chw,
                                                                  float gs, float* __restrict__ ratio) {
@@ -558,6 +619,54 @@ int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const flo
         eps_in, x, d1, d2, d3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, order, sigma, c0, c1,
         c2, c3, d_out, x_prev, pred_x0);
     GMD_CHECK_LAUNCH("gmd_lms_step");
+    return GMD_OK;
+}
+
+int gmd_unipc_step(const float* eps_in, const float* x, const float* last_sample, const float* h1, const float* h2, const float* h3, int B,
+                   int64_t chw, int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale, int corr_order,
+                   int pred_order, float sigma_s, float alpha_s, float c_x, float c_m, float c_b, float c_rho1, float c_rho2, float c_rho3,
+                   float c_r1, float c_r2, float p_x, float p_m, float p_b, float p_rho1, float p_rho2, float p_r1, float p_r2,
+                   float sqrt_alpha, float sqrt_one_minus_alpha, float* m0_out, float* x_corr, float* x_prev, float* x0,
+                   gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && chw > 0, "gmd_unipc_step: bad shape B=%d chw=%lld", B, (long long)chw);
+    GMD_REQUIRE(corr_order >= 0 && corr_order <= 3, "gmd_unipc_step: corrector order %d not in 0..3", corr_order);
+    GMD_REQUIRE(pred_order >= 1 && pred_order <= 3, "gmd_unipc_step: predictor order %d not in 1..3", pred_order);
+    GMD_REQUIRE(std::isfinite(sigma_s), "gmd_unipc_step: sigma_s must be finite (got %g)", (double)sigma_s);
+    GMD_REQUIRE(std::isfinite(alpha_s) && alpha_s != 0.0f, "gmd_unipc_step: alpha_s must be finite and non-zero (got %g)", (double)alpha_s);
+    GMD_REQUIRE(x0 == nullptr || (std::isfinite(sqrt_alpha) && sqrt_alpha != 0.0f && std::isfinite(sqrt_one_minus_alpha)),
+                "gmd_unipc_step: sqrt_alpha must be finite and non-zero, sqrt_one_minus_alpha finite, when x0 is asked for");
+    // a scalar beyond the order is never used, so it is not looked at: at predictor order 1 that includes p_b (-inf at the last step of
+    // a bh1 schedule that ends at sigma 0)
+    if (corr_order >= 1) {
+        const float c[3] = {c_x, c_m, c_b}, rho[3] = {c_rho1, c_rho2, c_rho3}, r[2] = {c_r1, c_r2};
+        const char* names[3] = {"c_x", "c_m", "c_b"};
+        for (int k = 0; k < 3; ++k) GMD_REQUIRE(std::isfinite(c[k]), "gmd_unipc_step: %s must be finite (got %g)", names[k], (double)c[k]);
+        for (int k = 0; k < corr_order; ++k)
+            GMD_REQUIRE(std::isfinite(rho[k]), "gmd_unipc_step: c_rho%d must be finite (got %g)", k + 1, (double)rho[k]);
+        for (int k = 0; k < corr_order - 1; ++k)
+            GMD_REQUIRE(std::isfinite(r[k]) && r[k] != 0.0f, "gmd_unipc_step: c_r%d must be finite and non-zero (got %g)", k + 1, (double)r[k]);
+    }
+    GMD_REQUIRE(std::isfinite(p_x), "gmd_unipc_step: p_x must be finite (got %g)", (double)p_x);
+    GMD_REQUIRE(std::isfinite(p_m), "gmd_unipc_step: p_m must be finite (got %g)", (double)p_m);
+    if (pred_order >= 2) {
+        const float rho[2] = {p_rho1, p_rho2}, r[2] = {p_r1, p_r2};
+        GMD_REQUIRE(std::isfinite(p_b), "gmd_unipc_step: p_b must be finite (got %g)", (double)p_b);
+        for (int k = 0; k < pred_order - 1; ++k) {
+            GMD_REQUIRE(std::isfinite(rho[k]), "gmd_unipc_step: p_rho%d must be finite (got %g)", k + 1, (double)rho[k]);
+            GMD_REQUIRE(std::isfinite(r[k]) && r[k] != 0.0f, "gmd_unipc_step: p_r%d must be finite and non-zero (got %g)", k + 1, (double)r[k]);
+        }
+    }
+    if (B == 0) return GMD_OK;
+    GMD_REQUIRE(eps_in && x && m0_out && x_corr && x_prev, "gmd_unipc_step: null pointer");
+    GMD_REQUIRE(corr_order < 1 || last_sample, "gmd_unipc_step: corrector order %d needs last_sample", corr_order);
+    GMD_REQUIRE((corr_order < 1 && pred_order < 2) || h1, "gmd_unipc_step: corrector order %d / predictor order %d needs h1", corr_order, pred_order);
+    GMD_REQUIRE((corr_order < 2 && pred_order < 3) || h2, "gmd_unipc_step: corrector order %d / predictor order %d needs h2", corr_order, pred_order);
+    GMD_REQUIRE(corr_order < 3 || h3, "gmd_unipc_step: corrector order 3 needs h3");
+    unipc_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
+        eps_in, x, last_sample, h1, h2, h3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, corr_order,
+        pred_order, sigma_s, alpha_s, c_x, c_m, c_b, c_rho1, c_rho2, c_rho3, c_r1, c_r2, p_x, p_m, p_b, p_rho1, p_rho2, p_r1, p_r2,
+        sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_corr, x_prev, x0);
+    GMD_CHECK_LAUNCH("gmd_unipc_step");
     return GMD_OK;
 }
 

@@ -9,11 +9,11 @@ from .clip_text_model import CLIPTextModel
 from .configuration import ConfigMixin, FrozenDict
 from .image_processor import StableDiffusionPipelineOutput, VaeImageProcessor, randn_tensor
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
-                         LCMScheduler, LMSDiscreteScheduler, PNDMScheduler)
+                         LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
 from .unet_2d_condition import UNet2DConditionModel
 
 __all__ = [
     "AutoencoderKL", "UNet2DConditionModel", "CLIPTextModel", "PNDMScheduler", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "EulerDiscreteScheduler",
-    "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "LCMScheduler", "VaeImageProcessor",
+    "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "LCMScheduler", "UniPCMultistepScheduler", "VaeImageProcessor",
     "StableDiffusionPipelineOutput", "randn_tensor", "FrozenDict", "ConfigMixin",
 ]

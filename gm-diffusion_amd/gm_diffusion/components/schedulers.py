@@ -2,7 +2,7 @@
 Schedulers for the MI355X build: ``PNDMScheduler`` (PLMS, the "50 PNDM steps" configuration of
 scripts/stage2/train_gm_unet.py:171-176), ``DDPMScheduler`` (scripts/inference/generate_hdr.py:162),
 ``DDIMScheduler`` (scripts/stage2/train_gm_unet.py:48, scheduler_tuning.py:178-188),
-``LCMScheduler`` (few-step sampling of a guidance-embedded UNet), ``DPMSolverMultistepScheduler`` and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` /
+``LCMScheduler`` (few-step sampling of a guidance-embedded UNet), ``DPMSolverMultistepScheduler``, ``UniPCMultistepScheduler`` (predictor-corrector) and the sigma-space ``EulerDiscreteScheduler`` / ``EulerAncestralDiscreteScheduler`` /
 ``LMSDiscreteScheduler`` (the only ones whose ``init_noise_sigma`` and ``scale_model_input`` do something).  In the reference they come from ``diffusers``; these
 classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241, 610-625, 715,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
@@ -1308,3 +1308,217 @@ class LMSDiscreteScheduler(_SigmaSchedulerBase):
         self._keep(derivative, order)
         prev = sample + sum(coeff * derivative for coeff, derivative in zip(lms_coeffs, reversed(self.derivatives)))
         return self._finish(prev, p0, return_dict)
+
+
+class _UniPCPlan:
+    """The scalars of one UniPC step, each a float32 0-d CPU tensor: corrector order ``p`` (0 = off) with ``c_x, c_m, c_b``, ``c_rho``
+    (p entries) and ``c_r`` (p - 1 entries), predictor order ``q`` with ``p_x, p_m, p_b``, ``p_rho`` and ``p_r`` (q - 1 entries each)."""
+
+    __slots__ = ("p", "q", "sigma_s", "alpha_s", "c_x", "c_m", "c_b", "c_rho", "c_r", "p_x", "p_m", "p_b", "p_rho", "p_r")
+
+    def floats(self):
+        """The 17 scheduler scalars of gmd_unipc_step in its order; a slot beyond the orders in use is 0.0 (the kernel never reads it)."""
+        pad = lambda v, k: [t.item() for t in v] + [0.0] * (k - len(v))
+        corr = ([self.c_x.item(), self.c_m.item(), self.c_b.item()] + pad(self.c_rho, 3) + pad(self.c_r, 2)) if self.p else [0.0] * 8
+        pred = [self.p_x.item(), self.p_m.item(), self.p_b.item() if self.q > 1 else 0.0] + pad(self.p_rho, 2) + pad(self.p_r, 2)
+        return [self.sigma_s.item(), self.alpha_s.item()] + corr + pred
+
+
+class UniPCMultistepScheduler(_SchedulerBase):
+    """UniPC (Zhao et al. 2023, diffusers' ``UniPCMultistepScheduler``): a multistep predictor of order 1-3 whose previous update is
+    repaired by a corrector that re-uses the model output of the CURRENT step, so the correction costs no UNet evaluation.  The sampler
+    for 8-20 steps with an ordinary checkpoint.  Implemented: ``predict_x0`` with epsilon prediction, ``solver_type`` bh1 / bh2,
+    ``solver_order`` 1-3, ``lower_order_final``, ``disable_corrector``, ``final_sigmas_type`` zero / sigma_min, the three spacings;
+    Karras / exponential / beta / flow sigmas, ``predict_x0=False``, ``solver_p``, thresholding, zero-SNR betas and other prediction
+    types raise NotImplementedError.  Variance-preserving: ``init_noise_sigma`` is 1 and ``scale_model_input`` the identity; tables and
+    the step-index rule are ``DPMSolverMultistepScheduler``'s.  A host-side state machine: ``step`` / ``fused_step`` run as ONE HIP
+    kernel (gmd_unipc_step: x0, corrector and predictor) for float32 device tensors, as the torch expressions of ``_host_step``
+    otherwise.
+
+    Two deliberate differences from diffusers.  The weighted sum over the history differences is written as float32 products and adds
+    from left to right (the corrector's ``x0 - m0`` term last) where diffusers calls ``einsum``: equal up to rounding, and reproducible
+    bit for bit by the kernel.  At order 1 the ``B_h`` term is omitted, not multiplied by a zero: at the last step of a schedule that
+    ends at sigma 0, h is +inf and diffusers' bh1 multiplies -inf by the integer 0 there."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, predict_x0=True, solver_type="bh2", lower_order_final=True, disable_corrector=[],
+                     solver_p=None, use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False, use_flow_sigmas=False,
+                     flow_shift=1.0, timestep_spacing="linspace", steps_offset=0, final_sigmas_type="zero", rescale_betas_zero_snr=False,
+                     clip_sample=False)
+    MAX_ORDER = 3  # gmd_unipc_step reads at most three earlier x0 predictions
+
+    def __init__(self, **kwargs):
+        cfg = dict(self._defaults)
+        bad = [k for k in kwargs if k not in cfg]
+        if bad:
+            raise TypeError(f"UniPCMultistepScheduler: unexpected arguments {bad}")
+        cfg.update(kwargs)
+        cfg["disable_corrector"] = list(cfg["disable_corrector"] or [])
+        if cfg["solver_type"] in ("midpoint", "heun", "logrho"):  # another solver's config (from_config): diffusers falls to bh2 too
+            cfg["solver_type"] = "bh2"
+        self.register_to_config(**cfg)
+        for key in ("use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "use_flow_sigmas", "thresholding",
+                    "rescale_betas_zero_snr"):
+            if cfg[key]:
+                raise NotImplementedError(f"UniPCMultistepScheduler: {key}=True is not implemented")
+        if not cfg["predict_x0"]:
+            raise NotImplementedError("UniPCMultistepScheduler: predict_x0=False is not implemented")
+        if cfg["solver_p"] is not None:
+            raise NotImplementedError("UniPCMultistepScheduler: solver_p is not implemented")
+        if cfg["prediction_type"] != "epsilon":
+            raise NotImplementedError(f"UniPCMultistepScheduler: prediction_type={cfg['prediction_type']!r} is not implemented (epsilon only)")
+        if cfg["solver_type"] not in ("bh1", "bh2"):
+            raise NotImplementedError(f"UniPCMultistepScheduler: solver_type={cfg['solver_type']!r} is not implemented (bh1, bh2)")
+        if cfg["solver_order"] not in (1, 2, 3):
+            raise NotImplementedError(f"UniPCMultistepScheduler: solver_order={cfg['solver_order']!r} is not implemented (1..{self.MAX_ORDER})")
+        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self.sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
+        self.init_noise_sigma = 1.0
+        self.num_inference_steps = None
+        self.timesteps = torch.from_numpy(np.linspace(0, cfg["num_train_timesteps"] - 1, cfg["num_train_timesteps"], dtype=np.float32)[::-1].copy())
+        self.model_outputs = [None] * cfg["solver_order"]
+        self.lower_order_nums = 0
+        self.last_sample = None
+        self.this_order = None
+        self._step_index = None
+
+    @property
+    def step_index(self):
+        return self._step_index
+
+    def set_timesteps(self, num_inference_steps=None, device=None):
+        """The timestep and sigma tables of ``DPMSolverMultistepScheduler.set_timesteps`` (same config keys, same arithmetic), which
+        also clears ``model_outputs``, ``lower_order_nums`` and the step index."""
+        DPMSolverMultistepScheduler.set_timesteps(self, num_inference_steps, device)
+        self.last_sample = None
+        self.this_order = None
+
+    _init_step_index = DPMSolverMultistepScheduler._init_step_index
+
+    def draws_noise(self, timestep):
+        """False: the step is deterministic and never consumes a generator."""
+        return False
+
+    def _lambda(self, k):
+        """(alpha, sigma, lambda) of sigma-table entry k as float32 0-d tensors."""
+        alpha, sigma = DPMSolverMultistepScheduler._sigma_to_alpha_sigma_t(self.sigmas[k])
+        return alpha, sigma, torch.log(alpha) - torch.log(sigma)
+
+    def _rb(self, h, rks):
+        """(R, b, phi_1, B_h) of the UniPC paper's linear system for step size ``h`` and the nodes ``rks`` (the last one is 1)."""
+        hh = -h
+        phi_1 = torch.expm1(hh)
+        B_h = hh if self.config.solver_type == "bh1" else torch.expm1(hh)
+        rks = torch.stack(rks)
+        h_phi_k = phi_1 / hh - 1
+        f = 1
+        R, b = [], []
+        for j in range(1, len(rks) + 1):
+            R.append(torch.pow(rks, j - 1))
+            b.append(h_phi_k * f / B_h)
+            f *= j + 1
+            h_phi_k = h_phi_k / hh - 1 / f
+        return torch.stack(R), torch.stack(b), phi_1, B_h
+
+    def _plan_step(self, timestep):
+        """Host side of one step: a ``_UniPCPlan``.  Reads the state, changes nothing but the step index's initialisation."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        if self._step_index is None:
+            self._init_step_index(timestep)
+        c = self.config
+        i, n = self._step_index, len(self._ts_host)
+        pl = _UniPCPlan()
+        alpha_s, sigma_s, lambda_s = self._lambda(i)
+        pl.sigma_s, pl.alpha_s = sigma_s, alpha_s
+        one = torch.tensor(1.0)
+        # corrector: repairs the update from sigma_{i-1} to sigma_i with the order that update was predicted with
+        pl.p = self.this_order if (i > 0 and (i - 1) not in c.disable_corrector and self.last_sample is not None) else 0
+        if pl.p:
+            _, sigma_p, lambda_p = self._lambda(i - 1)
+            h = lambda_s - lambda_p
+            pl.c_r = [(self._lambda(i - 1 - k)[2] - lambda_p) / h for k in range(1, pl.p)]
+            R, b, phi_1, B_h = self._rb(h, pl.c_r + [one])
+            pl.c_rho = [torch.tensor(0.5)] if pl.p == 1 else list(torch.linalg.solve(R, b))
+            pl.c_x, pl.c_m, pl.c_b = sigma_s / sigma_p, alpha_s * phi_1, alpha_s * B_h
+        # predictor
+        q = min(c.solver_order, n - i) if c.lower_order_final else c.solver_order
+        pl.q = q = min(q, self.lower_order_nums + 1)
+        alpha_t, sigma_t, lambda_t = self._lambda(i + 1)
+        h = lambda_t - lambda_s
+        if q > 1 and not torch.isfinite(h):
+            raise ValueError(f"UniPCMultistepScheduler: the last step ends at sigma 0 (h is not finite) and would run at order {q}, whose"
+                             " coefficients are not finite; use lower_order_final=True or final_sigmas_type=\"sigma_min\"")
+        pl.p_r = [(self._lambda(i - k)[2] - lambda_s) / h for k in range(1, q)]
+        R, b, phi_1, B_h = self._rb(h, pl.p_r + [one])
+        pl.p_rho = [] if q == 1 else [torch.tensor(0.5)] if q == 2 else list(torch.linalg.solve(R[:-1, :-1], b[:-1]))
+        pl.p_x, pl.p_m, pl.p_b = sigma_t / sigma_s, alpha_t * phi_1, alpha_t * B_h
+        return pl
+
+    def _advance(self, x0_pred, corrected, pl):
+        c = self.config
+        for k in range(c.solver_order - 1):
+            self.model_outputs[k] = self.model_outputs[k + 1]
+        self.model_outputs[-1] = x0_pred
+        self.this_order = pl.q
+        self.last_sample = corrected
+        if self.lower_order_nums < c.solver_order:
+            self.lower_order_nums += 1
+        self._step_index += 1
+
+    def _device_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0):
+        """One HIP kernel pass (gmd_unipc_step): CFG combine (+rescale), pipeline x0, x0 prediction, corrector and predictor.  What is
+        kept as history (the x0 prediction and the corrected sample) are the kernel's own outputs, never ``eps_in`` (which may be the
+        static output buffer of a captured graph) nor the caller's ``sample``.  Returns (prev_sample, x0 | None)."""
+        pl = self._plan_step(timestep)
+        a = self.alphas_cumprod[int(timestep)]  # the pipeline's own x0 (dual_unet.py:1072) uses the loop timestep
+        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        hist = list(reversed(self.model_outputs))[:max(pl.p, pl.q - 1)]
+        m0, corrected, prev, x0 = ops.unipc_step(eps_in.contiguous(), sample.contiguous(), pl.p, pl.q,
+                                                 pl.floats() + [a.sqrt().item(), (1 - a).sqrt().item()], do_cfg, guidance_scale,
+                                                 last_sample=self.last_sample if pl.p else None, hist=hist, ratio=ratio,
+                                                 guidance_rescale=guidance_rescale, want_x0=want_x0)
+        self._advance(m0, corrected, pl)
+        return prev, x0
+
+    def fused_step(self, eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale=0.0, want_x0=False, generator=None, noise=None):
+        """Same contract as ``DPMSolverMultistepScheduler.fused_step`` (device float32 tensors only); ``generator`` and ``noise`` are
+        accepted and unused.  Returns (prev_sample, x0 | None)."""
+        return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0)
+
+    def step(self, model_output, timestep, sample, return_dict=True):
+        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+            prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False)
+        else:
+            prev = self._host_step(model_output, timestep, sample)
+        return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
+
+    def _host_step(self, model_output, timestep, sample):
+        """The step as torch expressions (host tensors and 16-bit device tensors; also the reference for the kernel tests): float32
+        throughout, every scalar a float32 0-d tensor, sums from left to right.  Returns prev_sample."""
+        pl = self._plan_step(timestep)
+        eps, x = model_output.to(torch.float32), sample.to(torch.float32)
+        x0_pred = (x - pl.sigma_s * eps) / pl.alpha_s  # from the sample as it comes in
+        if pl.p:
+            m0 = self.model_outputs[-1]
+            acc = None
+            for k in range(1, pl.p):
+                term = pl.c_rho[k - 1] * ((self.model_outputs[-(k + 1)] - m0) / pl.c_r[k - 1])
+                acc = term if acc is None else acc + term
+            term = pl.c_rho[pl.p - 1] * (x0_pred - m0)
+            acc = term if acc is None else acc + term
+            x = pl.c_x * self.last_sample - pl.c_m * m0 - pl.c_b * acc
+        elif x is sample:
+            x = x.clone()  # kept as last_sample: never the caller's own tensor
+        self._advance(x0_pred, x, pl)
+        prev = pl.p_x * x - pl.p_m * x0_pred
+        if pl.q > 1:
+            acc = None
+            for k in range(1, pl.q):
+                term = pl.p_rho[k - 1] * ((self.model_outputs[-(k + 1)] - x0_pred) / pl.p_r[k - 1])
+                acc = term if acc is None else acc + term
+            prev = prev - pl.p_b * acc
+        return prev.to(model_output.dtype)

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -1246,6 +1246,38 @@ def lms_step(eps_in, x, order, coefs, do_cfg, guidance_scale, hist=(), ratio=Non
                              _ptr(ratio), float(guidance_rescale), order, sg, c0, c1, c2, c3, _ptr(d), _ptr(x_prev), _ptr(pred_x0),
                              _stream()), "gmd_lms_step")
     return d, x_prev, pred_x0
+
+
+def unipc_step(eps_in, x, corr_order, pred_order, coefs, do_cfg, guidance_scale, last_sample=None, hist=(), ratio=None, guidance_rescale=0.0,
+               want_x0=False):
+    """Fused CFG + UniPC corrector (order 0 = off .. 3) + predictor (order 1-3) update.  coefs = the 19 floats of gmd_unipc_step in its
+    order: (sigma_s, alpha_s, c_x, c_m, c_b, c_rho1, c_rho2, c_rho3, c_r1, c_r2, p_x, p_m, p_b, p_rho1, p_rho2, p_r1, p_r2, sqrt_alpha,
+    sqrt_one_minus_alpha).  ``hist``: the x0 predictions of the previous steps, newest first (at most three are passed on);
+    ``last_sample``: the corrected sample of the previous step.  Returns (m0, x_corr, x_prev, x0|None), all allocated here, so what the
+    caller keeps as history is never the static buffer of a captured graph nor the caller's own sample."""
+    _dev(eps_in, x, last_sample, ratio, *hist)
+    for t in (eps_in, x, last_sample, *hist):
+        _f32(t, "latent tensors")
+    p, q = int(corr_order), int(pred_order)
+    need = max(p, q - 1)
+    if len(hist) < need:
+        raise HipExtensionError(f"unipc_step: corrector order {p} / predictor order {q} needs {need} earlier x0 predictions (got {len(hist)})")
+    if p >= 1 and last_sample is None:
+        raise HipExtensionError(f"unipc_step: corrector order {p} needs last_sample")
+    if any(h.shape != x.shape for h in (*hist, *(() if last_sample is None else (last_sample,)))):
+        raise HipExtensionError("unipc_step: history tensors and last_sample must have the sample's shape")
+    c = [float(v) for v in coefs]
+    if len(c) != 19:
+        raise HipExtensionError(f"unipc_step: 19 coefficients expected (got {len(c)})")
+    B = x.shape[0]
+    chw = x.shape[1:].numel()
+    m0, x_corr, x_prev = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
+    x0 = torch.empty_like(x) if want_x0 else None
+    h = list(hist[:3]) + [None] * (3 - len(hist[:3]))
+    check(lib().gmd_unipc_step(_ptr(eps_in), _ptr(x), _ptr(last_sample), _ptr(h[0]), _ptr(h[1]), _ptr(h[2]), B, chw, int(do_cfg),
+                               float(guidance_scale), _ptr(ratio), float(guidance_rescale), p, q, *c, _ptr(m0), _ptr(x_corr), _ptr(x_prev),
+                               _ptr(x0), _stream()), "gmd_unipc_step")
+    return m0, x_corr, x_prev, x0
 
 
 # ----------------------------------------------------------------------------------------------

@@ -15,7 +15,8 @@ import os
 import torch
 
 from ..components import (AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                          EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel)
+                          EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel,
+                          UniPCMultistepScheduler)
 from ..components.configuration import FrozenDict
 
 _LOADABLE = {
@@ -30,6 +31,7 @@ _LOADABLE = {
     "EulerAncestralDiscreteScheduler": EulerAncestralDiscreteScheduler,
     "LMSDiscreteScheduler": LMSDiscreteScheduler,
     "LCMScheduler": LCMScheduler,  # what a latent-consistency checkpoint's scheduler/ folder names
+    "UniPCMultistepScheduler": UniPCMultistepScheduler,
 }
 
 

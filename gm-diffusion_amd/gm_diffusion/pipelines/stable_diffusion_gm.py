@@ -371,10 +371,11 @@ class _GMPipelineBase(DiffusionPipeline):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
         from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                                             EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler)
+                                             EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, UniPCMultistepScheduler)
 
         return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler, LCMScheduler,
-                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler))
+                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler,
+                                                            UniPCMultistepScheduler))
                 and isinstance(unet, UNet2DConditionModel))
 
     @staticmethod
@@ -399,7 +400,7 @@ class _GMPipelineBase(DiffusionPipeline):
         ~4 GB on the host AND on the device): the loop then draws per step, as the reference does.
         DDIM draws iff ``eta`` > 0, then at every step (the last included): every (step, scheduler) is a slot.  So does a
         ``DPMSolverMultistepScheduler`` with the SDE algorithm, and ``EulerAncestralDiscreteScheduler`` always; a deterministic
-        scheduler (``EulerDiscreteScheduler`` and ``LMSDiscreteScheduler`` among them) has nothing to pre-draw.  ``LCMScheduler`` draws
+        scheduler (``EulerDiscreteScheduler``, ``LMSDiscreteScheduler`` and ``UniPCMultistepScheduler`` among them) has nothing to pre-draw.  ``LCMScheduler`` draws
         at every step but the last, as DDPM does.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""

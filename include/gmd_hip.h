@@ -288,6 +288,28 @@ int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const flo
                  int order, float sigma, float c0, float c1, float c2, float c3,
                  float* d_out, float* x_prev, float* pred_x0, gmd_stream_t stream);
 
+/* UniPC predictor-corrector step (diffusers' UniPCMultistepScheduler: predict_x0, epsilon prediction, bh1 / bh2, orders 1-3) fused
+ * with the same CFG combine / rescale as gmd_latent_step, in the float32 operation order of the scheduler's torch expressions.
+ * h1, h2, h3: the x0 predictions of the previous 1, 2, 3 steps (m0_out of those launches); last_sample: x_corr of the previous launch.
+ *   m0 = (x - sigma_s*eps)/alpha_s                                   from x as it comes in, before the correction
+ *   corrector, order corr_order = p in 0..3 (0: off, x_corr = x):
+ *     acc = c_rho1*((h2 - h1)/c_r1) [+ c_rho2*((h3 - h1)/c_r2)] + c_rho<p>*(m0 - h1)       (p = 1: c_rho1*(m0 - h1) alone)
+ *     x_corr = c_x*last_sample - c_m*h1 - c_b*acc
+ *   predictor, order pred_order = q in 1..3:
+ *     x_prev = p_x*x_corr - p_m*m0 [- p_b*(p_rho1*((h1 - m0)/p_r1) [+ p_rho2*((h2 - m0)/p_r2)])]   (q = 1: no p_b term at all)
+ * c_x / p_x = sigma_t/sigma_s, c_m / p_m = alpha_t*phi_1, c_b / p_b = alpha_t*B_h of the corrected / predicted interval.  The kernel
+ * divides by r_k.  m0_out (the host's history), x_corr (the host's next last_sample: a copy of x when the corrector is off) and x_prev
+ * are always written; x0 (the pipeline's (x - sqrt_one_minus_alpha*eps)/sqrt_alpha) may be NULL.  No output may alias an input.
+ * A pointer or scalar beyond the orders in use is neither read nor checked.  Refused before any launch: an order out of range, a
+ * non-finite scalar or a zero divisor among those in use, a null pointer among those in use. */
+int gmd_unipc_step(const float* eps_in, const float* x, const float* last_sample, const float* h1, const float* h2, const float* h3,
+                   int B, int64_t chw, int do_cfg, float guidance_scale, const float* rescale_ratio, float guidance_rescale,
+                   int corr_order, int pred_order, float sigma_s, float alpha_s,
+                   float c_x, float c_m, float c_b, float c_rho1, float c_rho2, float c_rho3, float c_r1, float c_r2,
+                   float p_x, float p_m, float p_b, float p_rho1, float p_rho2, float p_r1, float p_r2,
+                   float sqrt_alpha, float sqrt_one_minus_alpha,
+                   float* m0_out, float* x_corr, float* x_prev, float* x0, gmd_stream_t stream);
+
 /* per-sample unbiased std of the text eps and of the guided eps -> ratio[b] = std_text/std_cfg
  * (rescale_noise_cfg, stable_diffusion_dual_unet.py:88-91) */
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale,
