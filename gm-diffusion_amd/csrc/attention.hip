@@ -16,6 +16,7 @@
 // ds_read_b128 (K) and ds_read_b64 (V^T) fragment reads are bank-conflict free.
 #include "gmd_common.h"
 
+#include <cstdlib>
 #include <type_traits>
 
 // attention_split.hip: float32 tensors, three float16 MFMA passes per contraction (GMD_F32S)
@@ -461,8 +462,17 @@ template <int N> __device__ __forceinline__ void attn_wait_vmcnt() { asm volatil
 #define ATTN40_PRIO_MFMA(x)
 #define ATTN40_PRIO_VALU(x)
 #endif
-template <typename HT>
+// Softmax paths of a tile: classic maximum-first (the fallback), lagged stabiliser (float16), fixed stabiliser (bfloat16).
+enum { kSmClassic = 0, kSmLagged = 1, kSmFixed = 2 };
+// kFixedStab (bfloat16 only): bfloat16 has float32's exponent range, so P = 2^(score - m) needs no particular m to fit the
+// type, and any m cancels exactly between the numerator and the row sum (both taken on the matrix core from the same
+// rounded P).  The stabiliser is therefore set ONCE per query row, to the maximum of the first tile, and a tile is: two
+// first products, exp2, pack, second product -- no row maximum, no alpha, no accumulator rescale.  float16's window is
+// 2^16 and keeps the lagged stabiliser.  A row whose sum leaves [0, 2^120) (a score ~120 log2 units above the row's
+// first-tile maximum, +inf, NaN) re-runs its block on the classic path, like a lagged overflow.
+template <typename HT, bool kFixedStab>
 __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
+    static_assert(!kFixedStab || std::is_same<HT, bf16_t>::value, "the fixed stabiliser needs float32's exponent range: bfloat16 only");
     GMD_WG_TRACE_SCOPE(WGK_ATTN40);
     constexpr int D = 40, DK = 3, DT = 2, NST = 3;
     constexpr int KROWB = 2 * D;                 // dense K row, bytes
@@ -470,7 +480,7 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
     constexpr int kVOff = 5376;                  // V^T rows (128 B each), 256-byte aligned
     constexpr int kStage = kVOff + (D + 2) * 128;  // + the ones row and the zero row
     static_assert(kLagOff + 16 <= kVOff && kStage % 256 == 0, "stage layout");
-    constexpr float kLagMax = std::is_same<HT, f16_t>::value ? 14.0f : 20.0f;
+    [[maybe_unused]] constexpr float kLagMax = std::is_same<HT, f16_t>::value ? 14.0f : 20.0f;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
@@ -620,8 +630,9 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
     };
 
     // one K / V^T tile out of ring stage STAGE
-    auto tile = [&](const int kt, auto stage_c, auto lag_c) {
-        constexpr bool LAG = decltype(lag_c)::value;
+    auto tile = [&](const int kt, auto stage_c, auto mode_c) {
+        constexpr int MODE = decltype(mode_c)::value;
+        constexpr bool LAG = MODE == kSmLagged;
         constexpr int STAGE = decltype(stage_c)::value;
         const int k0 = kt * KV;
         wait_tile(kt + 1 < ntiles);
@@ -663,12 +674,20 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
                     if (key >= p.Nk) st[t][i] = kNegBig;
                 }
         }
-        float mx = fmaxf(st[0][0], st[1][0]);
+        [[maybe_unused]] float mx, alpha;
+        if constexpr (MODE != kSmFixed) {
+            mx = fmaxf(st[0][0], st[1][0]);
 #pragma unroll
-        for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, st[0][i]), st[1][i]);
-        mx = half_swap_max(mx);
-        float alpha;
-        if constexpr (LAG) {
+            for (int i = 1; i < 16; ++i) mx = fmaxf(fmaxf(mx, st[0][i]), st[1][i]);
+            mx = half_swap_max(mx);
+        }
+        if constexpr (MODE == kSmFixed) {
+            // the accumulator is log2(p) relative to the row's one stabiliser: exp2, pack, second product
+#pragma unroll
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int i = 0; i < 16; ++i) st[t][i] = __builtin_amdgcn_exp2f(st[t][i]);
+        } else if constexpr (LAG) {
             lag_overflow |= mx > kLagMax;
 #pragma unroll
             for (int t = 0; t < 2; ++t)
@@ -722,12 +741,13 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
             }
         }
     };
-    auto run = [&](auto lag_c) {
-        constexpr bool LAG = decltype(lag_c)::value;
+    auto run = [&](auto stab_c) {
+        constexpr bool STAB = decltype(stab_c)::value;  // stabiliser through the matrix core (lagged or fixed), or classic
+        constexpr std::integral_constant<int, !STAB ? kSmClassic : (kFixedStab ? kSmFixed : kSmLagged)> mode_c{};
         issue(0, 0);
         if (ntiles > 1) issue(1, 1);
-        if constexpr (LAG) {
-            // initial stabiliser: the maximum of the first tile's scores (one extra first product)
+        if constexpr (STAB) {
+            // initial stabiliser (the only one, if fixed): the maximum of the first tile's scores (one extra first product)
             wait_tile(ntiles > 1);
             __syncthreads();
             float mx = kNegBig;
@@ -744,12 +764,16 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
             set_stabiliser(Half<HT>::round(mx));
         }
         for (int kt = 0; kt < ntiles; kt += 3) {
-            tile(kt, std::integral_constant<int, 0>{}, lag_c);
-            if (kt + 1 < ntiles) tile(kt + 1, std::integral_constant<int, 1>{}, lag_c);
-            if (kt + 2 < ntiles) tile(kt + 2, std::integral_constant<int, 2>{}, lag_c);
+            tile(kt, std::integral_constant<int, 0>{}, mode_c);
+            if (kt + 1 < ntiles) tile(kt + 1, std::integral_constant<int, 1>{}, mode_c);
+            if (kt + 2 < ntiles) tile(kt + 2, std::integral_constant<int, 2>{}, mode_c);
         }
     };
     run(std::true_type{});
+    // Overflow net of the fixed stabiliser: register 4 of O^T tile 1 is the row sum (d = 40) on the lower half-wave and the
+    // zero row (d = 44) on the upper.  A sum that is +inf, NaN (inf * 0 in the zero row as well) or so large that 1 / l
+    // would be subnormal sends the block down the classic path below.
+    if constexpr (kFixedStab) lag_overflow |= !(ot[1][4] < 0x1p120f);
     // A score more than 2^kLagMax above the lagged stabiliser could overflow exp2: redo the whole block with the classic
     // (maximum-first) softmax.  Block-wide decision (it is also the barrier that ends the last tile's LDS reads).
     if (__syncthreads_or(lag_overflow)) {
@@ -793,11 +817,25 @@ __global__ __launch_bounds__(256, 4) void attn40_kernel(const AttnParams p) {
     }
 }
 
+// GMD_ATTN40_FIXED=0 (read once) runs bfloat16 on the lagged-stabiliser instantiation as well: the A/B switch.
+bool attn40_fixed_enabled() {
+    static const bool on = [] {
+        const char* e = std::getenv("GMD_ATTN40_FIXED");
+        return !(e && e[0] == '0' && e[1] == '\0');
+    }();
+    return on;
+}
+
 template <typename HT>
 int launch_attn40(const AttnParams& p, int B, int H, hipStream_t s) {
     constexpr size_t smem = 3 * (5376 + 42 * 128);
     dim3 grid(((p.Nq + 127) / 128) * H * B, 1, 1);
-    attn40_kernel<HT><<<grid, 256, smem, s>>>(p);
+    if constexpr (std::is_same<HT, bf16_t>::value) {
+        if (attn40_fixed_enabled()) attn40_kernel<HT, true><<<grid, 256, smem, s>>>(p);
+        else attn40_kernel<HT, false><<<grid, 256, smem, s>>>(p);
+    } else {
+        attn40_kernel<HT, false><<<grid, 256, smem, s>>>(p);
+    }
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) {
         gmd_set_error("gmd_attention: launch failed: %s", hipGetErrorString(e));

@@ -527,7 +527,10 @@ int gmd_conv3x3_groupnorm(const void* X, const void* Wt, void* Yraw, void* Ynorm
 /* Flash-style attention, bf16 MFMA: O = softmax(scale * Q K^T) V per (batch, head).
  * Q: [B,Nq,*] head h at columns h*D..h*D+D, row stride ldq; K likewise (ldk);
  * Vt: V transposed, [B, H*D, ldvt] (keys contiguous, ldvt >= Nk, multiple of 8);
- * O: [B,Nq,H*D] row stride ldo.  D in {32,40,64,80,160}. */
+ * O: [B,Nq,H*D] row stride ldo.  D in {32,40,64,80,160}.
+ * D = 40, GMD_BF16: one softmax stabiliser per query row (the maximum of its first 64 keys), never updated -- bfloat16 has
+ * float32's exponent range; a row whose sum leaves [0, 2^120) re-runs its block maximum-first.  GMD_ATTN40_FIXED=0 in the
+ * environment (read once per process) selects the per-tile lagged stabiliser that GMD_F16 always uses: the A/B switch. */
 int gmd_attention(const void* Q, const void* K, const void* Vt, void* O, int dtype,
                   int B, int H, int D, int Nq, int Nk,
                   int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,

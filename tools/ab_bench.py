@@ -28,8 +28,11 @@ for r in range(a.rounds):
                     env[k] = val
         cmd = [sys.executable, os.path.join(tree, "bench.py"), "--steps", str(a.steps), "--warmup", str(a.warmup), "--no-cpu-baseline", "--no-drift",
                "--no-tolerance-path", "--no-kernel-timing"] + a.args.split()
-        out = subprocess.run(cmd, env=env, cwd=tree if tree != ROOT else None, capture_output=True, text=True).stdout
-        line = [l for l in out.splitlines() if l.startswith("{")]
+        p = subprocess.run(cmd, env=env, cwd=tree if tree != ROOT else None, capture_output=True, text=True)
+        if p.returncode != 0:  # a child that died is a finding, not a sample: start nothing after it
+            sys.exit(f"round {r} {v}: bench.py exited with {p.returncode}\n{p.stderr[-2000:]}")
+        out = p.stdout
+        line =[l for l in out.splitlines() if l.startswith("{")]
         ms = json.loads(line[-1])["ms_per_step"] if line else float("nan")
         res[v].append(ms)
         print(f"round {r} {v}: {ms} ms", flush=True)
