@@ -96,9 +96,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const GemmParams p) 
 // by the C/D layout (col = lane&15, row = 4*(lane>>4)+reg) a lane holds FOUR CONSECUTIVE output columns n of ONE
 // row m: bias/row-bias/residual/activation are applied in registers and each lane stores 8 bytes (bf16) or 16 bytes
 // (fp32 / split-K partials) -- no LDS round trip, no barrier.  mw/nw: first row/column of this wave's tile.
-template <typename HT, int TM, int TN>
+// UP2 (gemm_pp_kernel's phase mode, GemmParams::up2): mw counts the rows of phase `ph`; a row at or past up2_rows is skipped, the others
+// go to their output pixel (up2_out_row) and take the row bias of their sample.  Never with slabs (ksplit > 1: host-checked).
+template <typename HT, int TM, int TN, bool UP2 = false>
 __device__ __forceinline__ void epilogue_regs(const GemmParams& p, const f32x4 (&acc)[TM][TN], int mw, int nw, int frow, int fq,
-                                              int z, int ks) {
+                                              int z, int ks, int ph = 0) {
     const bool vec_c = (p.ldc % 4 == 0) && (p.sC % 4 == 0);
     const bool vec_r = p.residual != nullptr && (p.ldr % 4 == 0) && (p.sR % 4 == 0);
     const bool vec_n = (p.N % 4 == 0);
@@ -147,16 +149,23 @@ __device__ __forceinline__ void epilogue_regs(const GemmParams& p, const f32x4 (
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
-        const int m = mw + i * 16 + frow;
-        if (m >= p.M) continue;
-        const float* rb = p.rowbias ? p.rowbias + (int64_t)(m / p.rows_per_group) * p.ldrb : nullptr;
+        int64_t m = mw + i * 16 + frow;
+        int grp;
+        if constexpr (UP2) {
+            if (m >= p.up2_rows) continue;
+            m = up2_out_row(p, (int)m, ph, grp);
+        } else {
+            if (m >= p.M) continue;
+            grp = (int)m / p.rows_per_group;
+        }
+        const float* rb = p.rowbias ? p.rowbias + (int64_t)grp * p.ldrb : nullptr;
 #pragma unroll
         for (int j = 0; j < TN; ++j) {
             const int n = nw + j * 16 + fq * 4;
             if (n >= p.N) continue;
             const int nvalid = p.N - n < 4 ? p.N - n : 4;
             float v[4] = {acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]};
-            if (p.ksplit > 1) {  // raw partial sums; the epilogue runs in splitk_reduce_kernel
+            if (!UP2 && p.ksplit > 1) {  // raw partial sums; the epilogue runs in splitk_reduce_kernel
                 float* o = p.ws + ((int64_t)ks * p.M + m) * p.N + n;
                 if (nvalid == 4 && vec_n) *reinterpret_cast<float4*>(o) = make_float4(v[0], v[1], v[2], v[3]);
                 else
@@ -250,11 +259,14 @@ __device__ __forceinline__ void epilogue_cols_vt(const GemmParams& p, const f32x
 // division) sat in all ten unrolled items of a wave tile -- ~600 instructions, 3.6 KB of code per item -- and although their
 // branches were never taken, FETCHING that code once per wave tile cost ~0.55 us per item: in-kernel stamps put 5.5 of the 7.2 us
 // epilogue of a K = 320 projection there, with the stores, the bias and the residual all ruled out one by one (round 5).)
-template <typename HT, int TM, int TN, bool PLAIN>
+// UP2 (gemm_pp_kernel's phase mode, GemmParams::up2): mw counts the rows of phase `ph` and the whole wave tile lies below up2_rows;
+// a row goes to its output pixel (up2_out_row: store, residual), takes the row bias of its sample, and the wave tile's statistics
+// block is (sample 4 + phase) (Hin Win / 64) + its 64-row block inside the sample: a sample's blocks stay contiguous.
+template <typename HT, int TM, int TN, bool PLAIN, bool UP2 = false>
 __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f32x4 (&acc)[TM][TN], float* strip, int mw, int nw, int lane,
-                                                   int z) {
+                                                   int z, int ph = 0) {
     static_assert(TM % 2 == 0, "halves of two 16-row tiles");
-    if (p.vt_out && nw >= p.vt_col0) {  // wave-uniform: a V column tile of a fused Q|K|V projection
+    if (!UP2 && p.vt_out && nw >= p.vt_col0) {  // wave-uniform: a V column tile of a fused Q|K|V projection
         epilogue_cols_vt<HT, TM, TN>(p, acc, strip, mw, nw, lane);
         return;
     }
@@ -263,8 +275,10 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
     const int frow = lane & 15, fq = lane >> 4;
     // row-bias group (sample) of the wave tile's first row: ONE division per wave instead of one per stored item; a group
     // of at least 64 rows can change at most once inside the 64-row wave tile
+    Up2Tile ut{};  // UP2: the decoded first row of the wave tile
+    if constexpr (UP2) ut = up2_tile(p, __builtin_amdgcn_readfirstlane(mw));
     int g0 = 0, grem = 0;
-    if (p.rowbias) {
+    if (!UP2 && p.rowbias) {
         g0 = mw / p.rows_per_group;
         grem = mw - g0 * p.rows_per_group;
     }
@@ -303,7 +317,12 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
             const int idx = lane + 64 * t;
             const int r = idx / CH, c = idx - r * CH;
             if (32 * CH % 64 != 0 && r >= 32) continue;
-            resv[hh & 1][t] = *reinterpret_cast<const uint4*>((const HT*)p.residual + (int64_t)z * p.sR + (int64_t)(mw + hh * 32 + r) * p.ldr + nw + c * 8);
+            int64_t mo = mw + hh * 32 + r;
+            if constexpr (UP2) {
+                int smp;
+                mo = up2_tile_row(p, ut, hh * 32 + r, ph, smp);
+            }
+            resv[hh & 1][t] = *reinterpret_cast<const uint4*>((const HT*)p.residual + (int64_t)z * p.sR + mo * p.ldr + nw + c * 8);
         }
     };
     const bool res_pre = PLAIN && p.residual != nullptr;  // (the activation instances -- time-embedding MLP, text encoder: tiny launches -- load in place)
@@ -317,7 +336,9 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
                 const int r = idx / CH, c = idx - r * CH;
                 if (32 * CH % 64 != 0 && r >= 32) continue;
                 const int ro = h * 32 + r;
-                const int grp = p.rows_per_group >= 64 ? g0 + (grem + ro >= p.rows_per_group ? 1 : 0) : (mw + ro) / p.rows_per_group;
+                int grp;
+                if constexpr (UP2) up2_tile_row(p, ut, ro, ph, grp);
+                else grp = p.rows_per_group >= 64 ? g0 + (grem + ro >= p.rows_per_group ? 1 : 0) : (mw + ro) / p.rows_per_group;
                 const float* rb = p.rowbias + (int64_t)grp * p.ldrb + nw + c * 8;
                 resv[0][t] = __builtin_bit_cast(uint4, *reinterpret_cast<const float4*>(rb));
                 resv[1][t] = __builtin_bit_cast(uint4, *reinterpret_cast<const float4*>(rb + 4));
@@ -337,7 +358,10 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
             const int idx = lane + 64 * t;
             const int r = idx / CH, c = idx - r * CH;
             if (32 * CH % 64 != 0 && r >= 32) continue;
-            const int m = mw + h * 32 + r, n = nw + c * 8;
+            const int n = nw + c * 8;
+            int64_t m = mw + h * 32 + r;   // the output row
+            int smp = 0;                   // UP2: its sample
+            if constexpr (UP2) m = up2_tile_row(p, ut, h * 32 + r, ph, smp);
             const float4 a0 = *reinterpret_cast<const float4*>(strip + r * ROWF + c * 8);
             const float4 a1 = *reinterpret_cast<const float4*>(strip + r * ROWF + c * 8 + 4);
             float v[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
@@ -353,7 +377,7 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
                 add[0] += t0.x; add[1] += t0.y; add[2] += t0.z; add[3] += t0.w; add[4] += t1.x; add[5] += t1.y; add[6] += t1.z; add[7] += t1.w;
             } else if (p.rowbias) {  // row bias AND residual (never in the UNet): loaded in place
                 const int ro = h * 32 + r;  // row offset inside the wave tile
-                const int grp = p.rows_per_group >= 64 ? g0 + (grem + ro >= p.rows_per_group ? 1 : 0) : m / p.rows_per_group;
+                const int grp = UP2 ? smp : p.rows_per_group >= 64 ? g0 + (grem + ro >= p.rows_per_group ? 1 : 0) : (int)m / p.rows_per_group;
                 const float* rb = p.rowbias + (int64_t)grp * p.ldrb + n;
                 const float4 t0 = *reinterpret_cast<const float4*>(rb), t1 = *reinterpret_cast<const float4*>(rb + 4);
                 add[0] += t0.x; add[1] += t0.y; add[2] += t0.z; add[3] += t0.w; add[4] += t1.x; add[5] += t1.y; add[6] += t1.z; add[7] += t1.w;
@@ -408,9 +432,14 @@ __device__ __forceinline__ void epilogue_rows_impl(const GemmParams& p, const f3
 #undef EPI_STAMP
     // producer statistics for a following GroupNorm: {sum, sum of squares} of the STORED values over this wave tile's TM*16 = 64
     // rows (one row block of the statistics) and each bucket of cs_bucket adjacent columns
-    if (p.colstats)
-        colstats_store<NCOL, ROWF>(strip, lane, cs, cq, p.cs_bucket,
-                                   p.colstats + ((int64_t)(mw / (TM * 16)) * (p.N / p.cs_bucket) + nw / p.cs_bucket) * 2);
+    if (p.colstats) {
+        int64_t blk = mw / (TM * 16);
+        if constexpr (UP2) {  // (Hin Win is a multiple of 64 when statistics are asked for: host-checked)
+            const int bps = p.Hin * p.Win / (TM * 16), smp = (int)blk / bps;
+            blk = ((int64_t)smp * 4 + ph) * bps + ((int)blk - smp * bps);
+        }
+        colstats_store<NCOL, ROWF>(strip, lane, cs, cq, p.cs_bucket, p.colstats + (blk * (p.N / p.cs_bucket) + nw / p.cs_bucket) * 2);
+    }
 }
 
 template <typename HT, int TM, int TN>
@@ -1090,10 +1119,16 @@ __global__ __launch_bounds__(WM* WN * 64, (WM * WN) >= 4 ? (WM * WN) / 4 : 1) vo
 // arrive at #4kt; the DMA of tile kt+2 into that stage is issued after #4kt.  A loader's pieces of tile kt+1 have landed
 // (counted vmcnt) before it arrives at #4kt+4, and the first read of tile kt+1 (waves 0-3, R0) is issued after #4kt+4.
 // ------------------------------------------------------------------------------------------------
-template <typename HT, bool CONV, int TN>
+//
+// UP2 (CONV only; gmd_conv3x3_up2, GemmParams::up2): the nearest-2x upsampling convolution as four 2x2 phase convolutions over the
+// low-resolution image -- 4 taps instead of 9 per output pixel.  Only the loader's K walk (4 taps, their source pixels, the phase's
+// slab of W) and the addressing of the epilogue's rows differ; the main loop, its barriers and the MFMA schedule are the same code.
+template <typename HT, bool CONV, int TN, bool UP2 = false>
 __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
+    static_assert(CONV || !UP2, "the phase mode is a convolution");
     GMD_WG_TRACE_SCOPE(WGK_PP | (CONV ? WGK_CONV_BIT : 0));
     constexpr int WN = 2, NCONS = 8, LW = 4, TM = 4, NST = 3;
+    constexpr int NT = UP2 ? 4 : 9;                 // filter taps the conv loader walks
     constexpr int BM = 256, BN = WN * TN * 16;
     constexpr int RPP = LW * 8;                     // 32 tile rows per staging pass (8 rows per loader-wave instruction)
     constexpr int NA = BM / RPP;                    // 8 A pieces per loader wave and tile
@@ -1118,6 +1153,9 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
         m0 = mt * BM;
         n0 = nt * BN;
     }
+    // UP2: M-panel mt is panel mt / 4 of phase mt % 4; r0 = first row of the tile inside its phase (rows >= p.up2_rows do not exist)
+    const int ph = UP2 ? (m0 / BM) & 3 : 0;
+    const int r0 = UP2 ? ((m0 / BM) >> 2) * BM : m0;
     const int z = p.ksplit > 1 ? 0 : blockIdx.z;
     const int ks = p.ksplit > 1 ? blockIdx.z : 0;
     const int nk_total = p.K / BK;
@@ -1194,23 +1232,24 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
         bool pv[NA];
 #pragma unroll
         for (int i = 0; i < NA; ++i) {
-            const int m = m0 + srow + RPP * i;
-            pv[i] = m < p.M;
+            const int m = r0 + srow + RPP * i;
+            pv[i] = m < (UP2 ? p.up2_rows : p.M);
             pb[i] = py[i] = px[i] = 0;
             if (CONV) {
                 if (pv[i]) {
-                    const int hw = p.Hout * p.Wout;
-                    if (((hw & (hw - 1)) | (p.Wout & (p.Wout - 1))) == 0) {
-                        const int sh = __builtin_ctz(hw), sw = __builtin_ctz(p.Wout);
+                    const int iw = UP2 ? p.Win : p.Wout;  // UP2: rows are pixels of the low-resolution image
+                    const int hw = (UP2 ? p.Hin : p.Hout) * iw;
+                    if (((hw & (hw - 1)) | (iw & (iw - 1))) == 0) {
+                        const int sh = __builtin_ctz(hw), sw = __builtin_ctz(iw);
                         pb[i] = m >> sh;
                         const int rem = m & (hw - 1);
                         py[i] = rem >> sw;
-                        px[i] = rem & (p.Wout - 1);
+                        px[i] = rem & (iw - 1);
                     } else {
                         pb[i] = m / hw;
                         const int rem = m - pb[i] * hw;
-                        py[i] = rem / p.Wout;
-                        px[i] = rem - py[i] * p.Wout;
+                        py[i] = rem / iw;
+                        px[i] = rem - py[i] * iw;
                     }
                 }
                 aoff[i] = kOOB;
@@ -1221,16 +1260,17 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
 #pragma unroll
         for (int i = 0; i < NW; ++i) {
             const int n = n0 + srow + RPP * i;
-            woff[i] = n < p.N ? (unsigned)n * (unsigned)p.ldw * 2u + (unsigned)chunk * 16u : kOOB;
+            // (UP2: W is [4][N][ldw], one slab per phase; the whole of it is below kOOB: host-checked)
+            woff[i] = n < p.N ? (unsigned)(UP2 ? ph * p.N + n : n) * (unsigned)p.ldw * 2u + (unsigned)chunk * 16u : kOOB;
         }
-        // K position of the conv loader: (channel block cb0, tap 0..8, channel c0); tap == 9 is the K tail (GemmParams::A2), whose
-        // c0 counts the channels of A2 from 0.  All of it is wave-uniform.
+        // K position of the conv loader: (channel block cb0, tap 0..NT-1, channel c0); tap == 9 is the K tail (GemmParams::A2), whose
+        // c0 counts the channels of A2 from 0 (never in the phase mode).  All of it is wave-uniform.
         int tap = 0, c0 = 0, cb0 = 0;
         bool newtap = true;
         if (CONV) {
-            const int sb = p.cblk / BK, per_cb = 9 * sb, nconv = 9 * (p.Cin / BK);
+            const int sb = p.cblk / BK, per_cb = NT * sb, nconv = NT * (p.Cin / BK);
             if (kt_begin >= nconv) {  // this slice starts inside the tail
-                tap = 9;
+                tap = NT;
                 cb0 = p.Cin;
                 c0 = (kt_begin - nconv) * BK;
             } else {
@@ -1250,7 +1290,7 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
                        (unsigned)__builtin_amdgcn_readfirstlane(p.w_bytes), 0x00020000u};
         }
         u32x4 dA2 = dA;  // the K tail's operand (CONV with K2 > 0 only; never selected otherwise)
-        if (CONV && p.K2 > 0) {
+        if (CONV && !UP2 && p.K2 > 0) {
             const uint64_t b2 = (uint64_t)p.A2;
             dA2 = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((unsigned)b2), (unsigned)__builtin_amdgcn_readfirstlane((unsigned)(b2 >> 32) & 0xffffu),
                         (unsigned)__builtin_amdgcn_readfirstlane(p.a2_bytes), 0x00020000u};
@@ -1270,13 +1310,16 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
             constexpr int lo = Q == 4 ? 0 : Q * NP / 4, hi = Q == 4 ? NP : (Q + 1) * NP / 4;
             unsigned kbytes = (unsigned)(kt_begin + kt) * (BK * 2);
             unsigned abytes = kbytes;
-            const bool tail = CONV && tap == 9;  // wave-uniform: the descriptor below is a scalar select
+            const bool tail = CONV && !UP2 && tap == 9;  // wave-uniform: the descriptor below is a scalar select
             if (CONV) {
                 if ((Q == 0 || Q == 4) && newtap) {
                     if (tail) {  // rows of A2 at the output pixel itself
 #pragma unroll
                         for (int i = 0; i < NA; ++i)
                             aoff[i] = pv[i] ? (unsigned)(m0 + srow + RPP * i) * (unsigned)p.lda2 * 2u + (unsigned)chunk * 16u : kOOB;
+                    } else if constexpr (UP2) {
+#pragma unroll
+                        for (int i = 0; i < NA; ++i) aoff[i] = up2_tap_offset(p, pv[i], pb[i], py[i], px[i], ph, tap, chunk);
                     } else {
                         const int ky = tap / 3, kx = tap - ky * 3;
 #pragma unroll
@@ -1297,11 +1340,11 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
                 if (NA + i >= lo && NA + i < hi) dma16(dW, stage + BM * 128 + i * (RPP * 128), woff[i], kbytes);
             if (CONV && (Q == 3 || Q == 4)) {
                 c0 += BK;
-                if (tap < 9 && c0 >= cb0 + p.cblk) {
+                if (tap < NT && c0 >= cb0 + p.cblk) {
                     c0 = cb0;
                     ++tap;
                     newtap = true;
-                    if (tap == 9) {
+                    if (tap == NT) {
                         cb0 += p.cblk;
                         if (cb0 >= p.Cin) c0 = 0;            // the taps are done: what follows (if anything) is the tail
                         else { tap = 0; c0 = cb0; }
@@ -1441,6 +1484,23 @@ __global__ __launch_bounds__(768, 3) void gemm_pp_kernel(const GemmParams p) {
         q.ksplit = 1;
     }
     PP_PHASE_SYNC();
+    if constexpr (UP2) {
+        // per wave tile (64 rows of the phase): past the phase's rows -> nothing to store; whole -> row epilogue; else the register one
+        const int rw = r0 + wr * 64, nw = n0 + wc * (TN * 16);
+        if (rw >= q.up2_rows) return;
+        const bool rows_up = !q.out_f32 && q.ksplit <= 1 && q.act == GMD_ACT_NONE && rw + 64 <= q.up2_rows && n0 + BN <= q.N && (q.ldc & 7) == 0 &&
+                             (q.residual == nullptr || (q.ldr & 7) == 0) &&
+                             (q.rowbias == nullptr || ((q.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(q.rowbias) & 15) == 0)) &&
+                             (reinterpret_cast<uintptr_t>(q.bias) & 15) == 0;
+        if (__builtin_expect(rows_up, 1)) {
+            constexpr int kStrip = 32 * (TN * 16 + 4);
+            epilogue_rows_impl<HT, TM, TN, true, true>(q, acc, reinterpret_cast<float*>(smem) + wid * kStrip, rw, nw, lane, z, ph);
+        } else {
+            epilogue_regs<HT, TM, TN, true>(q, acc, rw, nw, frow, fq, z, ks, ph);
+        }
+        PP_PHASE_EMIT();
+        return;
+    }
     const bool rows_ok = !q.out_f32 && q.ksplit <= 1 && q.act != GMD_ACT_GEGLU && m0 + BM <= q.M && n0 + BN <= q.N && (q.ldc & 7) == 0 &&
                          (q.sC & 7) == 0 && (q.residual == nullptr || ((q.ldr & 7) == 0 && (q.sR & 7) == 0)) &&
                          (q.rowbias == nullptr || ((q.ldrb & 3) == 0 && (reinterpret_cast<uintptr_t>(q.rowbias) & 15) == 0)) &&
@@ -2411,14 +2471,14 @@ hipError_t launch_conv_patch(const GemmParams& p, bool continuous, int gz, hipSt
     return hipGetLastError();
 }
 
-template <typename HT, bool CONV, int TN>
+template <typename HT, bool CONV, int TN, bool UP2 = false>
 hipError_t launch_pp(const GemmParams& p, int gz, hipStream_t s) {
     constexpr int BM = 256, BN = 2 * TN * 16;
     constexpr size_t smem = (size_t)3 * (BM + BN) * 128;
-    hipError_t e = opt_in_lds(reinterpret_cast<const void*>(&gemm_pp_kernel<HT, CONV, TN>), (int)smem);
+    hipError_t e = opt_in_lds(reinterpret_cast<const void*>(&gemm_pp_kernel<HT, CONV, TN, UP2>), (int)smem);
     if (e != hipSuccess) return e;
     dim3 grid(((p.N + BN - 1) / BN) * ((p.M + BM - 1) / BM), 1, gz);
-    gemm_pp_kernel<HT, CONV, TN><<<grid, 768, smem, s>>>(p);
+    gemm_pp_kernel<HT, CONV, TN, UP2><<<grid, 768, smem, s>>>(p);
     return hipGetLastError();
 }
 
@@ -2518,6 +2578,32 @@ int launch_half(GemmParams p, int batch, void* ws, int64_t ws_bytes, hipStream_t
     }
     if (e != hipSuccess) {
         gmd_set_error("%s: launch failed: %s", name, hipGetErrorString(e));
+        return GMD_ERR_LAUNCH;
+    }
+    return GMD_OK;
+}
+
+// gmd_conv3x3_up2: the phase mode of gemm_pp_kernel<CONV> under its own plan (gemm_plan.cpp: up2_plan)
+template <typename HT>
+int launch_up2(GemmParams p, const Plan& pl, void* ws, int64_t ws_bytes, hipStream_t s) {
+    const PlanConfig cfg = plan_config();
+    p.ksplit = pl.ksplit;
+    p.ws = (float*)ws;
+    p.tile_group = 1;  // n fastest, then the four phases of an M-panel: they read the same source rows
+    p.fixup = 0;
+    if (pl.ksplit > 1) {  // (up2_plan keeps K slices only where the in-kernel reduction takes them)
+        if (!fixup_plan_ok(cfg, pl, p.M, p.N, ws ? ws_bytes : 0, false)) {
+            gmd_set_error("gmd_conv3x3_up2: plan %dx%d ksplit=%d has no in-kernel reduction", pl.bm, pl.bn, pl.ksplit);
+            return GMD_ERR_UNSUPPORTED;
+        }
+        p.fixup = 1;
+        p.fix_bytes = (unsigned)fixup_bytes(pl, p.M, p.N);
+        p.fix_cnt = reinterpret_cast<unsigned*>(reinterpret_cast<char*>(ws) + ws_bytes);  // the tail behind the usable bytes
+    }
+    const int gz = pl.ksplit > 1 ? pl.ksplit : 1;
+    const hipError_t e = pl.bn == 160 ? launch_pp<HT, true, 5, true>(p, gz, s) : launch_pp<HT, true, 4, true>(p, gz, s);
+    if (e != hipSuccess) {
+        gmd_set_error("gmd_conv3x3_up2: launch failed: %s", hipGetErrorString(e));
         return GMD_ERR_LAUNCH;
     }
     return GMD_OK;
@@ -2729,6 +2815,45 @@ int gmd_conv3x3(const void* X, const void* Wt, void* Y, int dtype, int out_dtype
                 float alpha, float* colstats, int colstats_bucket, void* workspace, int64_t workspace_bytes, gmd_stream_t stream) {
     return conv3x3_impl(X, Wt, Y, dtype, out_dtype, B, Hin, Win, Cin, Cout, stride, upsample, pad_mode, bias, rowbias, ldrb, residual, alpha,
                         colstats, colstats_bucket, workspace, gmd_ws_usable_bytes(workspace_bytes), stream, nullptr);
+}
+
+// conv3x3 of the nearest-2x upsampled image as four 2x2 phase convolutions over the low-resolution image (4/9 of the products).
+// Wp: [4][Cout][4 Cin], phase 2 py + px, tap-major (a, b) inside a phase, the nine-tap weights of the taps that read the same source
+// pixel summed (hip_ops.pack_upsample_phases).  Refused (GMD_ERR_UNSUPPORTED) where gmd_conv3x3_up2_plan answers 0.
+int gmd_conv3x3_up2(const void* X, const void* Wp, void* Y, int dtype, int out_dtype, int B, int Hin, int Win, int Cin, int Cout,
+                    const float* bias, const float* rowbias, int64_t ldrb, const void* residual, float* colstats, int colstats_bucket,
+                    void* workspace, int64_t workspace_bytes, gmd_stream_t stream) {
+    workspace_bytes = gmd_ws_usable_bytes(workspace_bytes);  // the tail of the workspace holds the split-K arrival counters
+    GMD_REQUIRE(gmd_is_half(dtype), "gmd_conv3x3_up2: the 16-bit types only (dtype %d)", dtype);
+    GMD_REQUIRE(out_dtype == GMD_F32 || out_dtype == dtype, "gmd_conv3x3_up2: out_dtype must be F32 or the input dtype");
+    GMD_REQUIRE(B >= 0 && Hin > 0 && Win > 0 && Cin > 0 && Cout > 0, "gmd_conv3x3_up2: bad shape");
+    if (B == 0) return GMD_OK;  // empty batch
+    GMD_REQUIRE(Cin % 64 == 0, "gmd_conv3x3_up2: Cin=%d must be a multiple of 64", Cin);
+    GMD_REQUIRE(X && Wp && Y && gmd_aligned16(X) && gmd_aligned16(Wp) && gmd_aligned16(Y), "gmd_conv3x3_up2: null or unaligned pointer");
+    GMD_REQUIRE(bias == nullptr || gmd_aligned16(bias), "gmd_conv3x3_up2: bias must be 16-byte aligned (it is read with float4 loads)");
+    GMD_REQUIRE(residual == nullptr || (gmd_aligned16(residual) && out_dtype == dtype), "gmd_conv3x3_up2: unaligned residual, or out_dtype != dtype with one");
+    GMD_REQUIRE(colstats == nullptr || (colstats_bucket > 0 && out_dtype == dtype && Cout % colstats_bucket == 0),
+                "gmd_conv3x3_up2: column statistics need a bucket dividing Cout and out_dtype == dtype");
+    Plan pl{};
+    int M = 0;
+    if (!up2_plan(plan_config(), dtype, B, Hin, Win, Cin, Cout, colstats ? colstats_bucket : 0, workspace ? workspace_bytes : 0, pl, M)) {
+        gmd_set_error("gmd_conv3x3_up2: B=%d %dx%d %d->%d%s has no phase launch under this plan family (ask gmd_conv3x3_up2_plan first)", B, Hin, Win,
+                      Cin, Cout, colstats ? " with column statistics" : "");
+        return GMD_ERR_UNSUPPORTED;
+    }
+    GemmParams p{};
+    p.A = X; p.W = Wp; p.C = Y; p.M = M; p.N = Cout; p.K = 4 * Cin;
+    p.lda = Cin; p.ldw = 4 * (int64_t)Cin; p.ldc = Cout;
+    p.a_bytes = (unsigned)((int64_t)B * Hin * Win * Cin * 2); p.w_bytes = (unsigned)(16LL * Cout * Cin * 2);  // (< 4 GiB: up2_plan)
+    p.bias = bias; p.rowbias = rowbias; p.rows_per_group = 4 * Hin * Win; p.ldrb = ldrb > 0 ? ldrb : Cout;
+    p.residual = residual; p.ldr = Cout; p.alpha = 1.0f; p.act = GMD_ACT_NONE;
+    p.out_f32 = out_dtype == GMD_F32;
+    p.Hin = Hin; p.Win = Win; p.Cin = Cin; p.Hout = 2 * Hin; p.Wout = 2 * Win; p.stride = 1; p.upsample = 1; p.pad_lo = 1;
+    p.cblk = conv_channel_block(plan_config(), B, Hin, Win, Cin, Cout, dtype);
+    p.colstats = colstats; p.cs_bucket = colstats_bucket;
+    p.up2 = 1; p.up2_rows = B * Hin * Win;
+    return dtype == GMD_BF16 ? launch_up2<bf16_t>(p, pl, workspace, workspace_bytes, (hipStream_t)stream)
+                             : launch_up2<f16_t>(p, pl, workspace, workspace_bytes, (hipStream_t)stream);
 }
 
 int gmd_conv3x3_tail(const void* X, const void* X2, const void* Wt, void* Y, int dtype, int out_dtype, int B, int Hin, int Win, int Cin, int K2,

@@ -62,6 +62,14 @@ struct GemmParams {
     int K2;
     int64_t lda2;
     unsigned a2_bytes;
+    // nearest-2x upsampling conv3x3 as four 2x2 phase convolutions (gmd_conv3x3_up2; gemm_pp_kernel<CONV, TN, UP2> only).  Output
+    // pixel (2i + py, 2j + px) reads the source pixels (i + a + py - 1, j + b + px - 1), a, b in {0, 1}, with the weights of the taps
+    // that hit the same source pixel summed on the host: K = 4 Cin, W = [4][N][4 Cin], phase z = 2 py + px.  up2_rows = B Hin Win
+    // GEMM rows per phase; M-panel mt of the launch is panel mt / 4 of phase mt % 4 (the phases of a panel are neighbours in the tile
+    // order: they read the same source rows), M = 4 ceil(up2_rows / 256) 256 counts the panels' rows, the rows at or past up2_rows of a
+    // phase's last panel are never loaded or stored.  Hout = 2 Hin, Wout = 2 Win.
+    int up2;
+    int up2_rows;
 };
 
 // The last GMD_WS_TAIL bytes of a caller's workspace hold the arrival counters of the in-kernel split-K reduction (one per tile):

@@ -413,6 +413,26 @@ int conv_plan_ksplit(const PlanConfig& cfg, int dtype, int64_t M, int Cin, int C
     return 1;
 }
 
+// Nearest-2x upsampling conv3x3 as four 2x2 phase convolutions: see gemm_plan.h.  make_plan is asked as for any GEMM of these
+// dimensions (no plan of an existing launch changes); a split the in-kernel reduction cannot take (more slices than fixup_max, no
+// workspace) is cut down, since the phase epilogue has no slab form.
+bool up2_plan(const PlanConfig& cfg, int dtype, int B, int Hin, int Win, int Cin, int Cout, int bucket, int64_t ws_bytes, Plan& pl, int& M) {
+    if (!is_half(dtype) || B <= 0 || Hin <= 0 || Win <= 0 || Cin <= 0 || Cout <= 0 || Cin % BK || bucket < 0) return false;
+    const int64_t rows = (int64_t)B * Hin * Win, mv = 4 * cdiv(rows, 256) * 256;
+    // 32-bit row indices and buffer offsets: output rows, the input and the four weight slabs
+    if (mv >= (1LL << 31) || rows * Cin * 2 >= 0xFFFF0000LL || 16LL * Cout * Cin * 2 >= 0xFFFF0000LL) return false;
+    M = (int)mv;
+    pl = make_plan(cfg, M, Cout, 4 * Cin, 1, ws_bytes, false, bucket > 0);
+    if (!(pl.pf == kPingPong && pl.bm == 256 && (pl.bn == 160 || pl.bn == 128)) || Cout % pl.bn) return false;
+    if (pl.ksplit > 1 && !fixup_plan_ok(cfg, pl, M, Cout, ws_bytes, false)) {
+        pl.ksplit = cfg.fixup_max >= 2 && pl.ksplit > cfg.fixup_max ? cfg.fixup_max : 1;
+        if (pl.ksplit > 1 && !fixup_plan_ok(cfg, pl, M, Cout, ws_bytes, false)) pl.ksplit = 1;
+    }
+    // statistics: 64-row wave tiles inside one sample, whole buckets per wave tile (80 or 64 columns)
+    if (bucket > 0 && (((int64_t)Hin * Win) % 64 || (pl.bn / 2) % bucket)) return false;
+    return true;
+}
+
 }  // namespace gmd
 
 // ---- the planner's part of the C ABI: overrides and plan queries ----
@@ -482,6 +502,15 @@ int gmd_gemm_plan_info(int dtype, int M, int N, int K, int batch, int64_t worksp
     const Plan pl = make_plan(plan_config(), M, N, K, batch, gmd_ws_usable_bytes(workspace_bytes), geglu != 0);
     out4[0] = pl.bm; out4[1] = pl.bn; out4[2] = pl.pf; out4[3] = pl.ksplit;
     return GMD_OK;
+}
+
+// 1 when gmd_conv3x3_up2 of these dimensions launches (out4, when given: tile rows, tile columns, kernel code, K slices)
+int gmd_conv3x3_up2_plan(int dtype, int B, int Hin, int Win, int Cin, int Cout, int colstats_bucket, int64_t workspace_bytes, int* out4) {
+    Plan pl{};
+    int M = 0;
+    if (!up2_plan(plan_config(), dtype, B, Hin, Win, Cin, Cout, colstats_bucket, gmd_ws_usable_bytes(workspace_bytes), pl, M)) return 0;
+    if (out4) { out4[0] = pl.bm; out4[1] = pl.bn; out4[2] = pl.pf; out4[3] = pl.ksplit; }
+    return 1;
 }
 
 // K slices of a float32 matrix-core (GMD_F32S / GMD_F32SW / GMD_F32SA) gmd_gemm_nt launch: slabs + splitk_reduce_f32_kernel when > 1

@@ -85,6 +85,12 @@ bool use_conv_patch(const PlanConfig& cfg, const Plan& pl, const GemmParams& p);
 bool conv_out_shape(int Hin, int Win, int stride, int& upsample, int pad_mode, int& Hout, int& Wout, int& pad_lo);
 int conv_plan_ksplit(const PlanConfig& cfg, int dtype, int64_t M, int Cin, int Cout, int64_t ws_bytes);
 
+// ---- nearest-2x upsampling conv3x3 as four 2x2 phase convolutions (gmd_conv3x3_up2) ----
+// The launch is planned as the GEMM it runs: M = 4 ceil(B Hin Win / 256) 256 rows (whole 256-row panels per phase), N = Cout,
+// K = 4 Cin.  True (and `pl`, `M` filled) when that plan is the 256-row ping-pong kernel, the only one with a phase loader; K slices
+// only where the in-kernel reduction takes them.  bucket > 0: the launch is to emit column statistics (false when it cannot).
+bool up2_plan(const PlanConfig& cfg, int dtype, int B, int Hin, int Win, int Cin, int Cout, int bucket, int64_t ws_bytes, Plan& pl, int& M);
+
 inline bool is_half(int dtype) { return dtype == GMD_BF16 || dtype == GMD_F16; }
 inline bool is_split(int dtype) { return dtype == GMD_F32S || dtype == GMD_F32SW || dtype == GMD_F32SA; }
 

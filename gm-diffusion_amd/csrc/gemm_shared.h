@@ -181,6 +181,58 @@ __device__ __forceinline__ unsigned conv_tap_offset(const GemmParams& p, bool va
     return (unsigned)(((b * p.Hin + iy) * p.Win + ix) * p.Cin) * 2u + (unsigned)chunk * 16u;
 }
 
+// Nearest-2x upsampling conv3x3 as four 2x2 phase convolutions (GemmParams::up2): tap (a, b) = (tap >> 1, tap & 1) of phase
+// (py, px) = (ph >> 1, ph & 1) at low-resolution pixel (i, j) reads source pixel (i + a + py - 1, j + b + px - 1).  A virtual pixel
+// outside [0, 2 Hin) is exactly a source pixel outside [0, Hin): the zero padding of the nine-tap form.
+__device__ __forceinline__ unsigned up2_tap_offset(const GemmParams& p, bool valid, int b, int i, int j, int ph, int tap, int chunk) {
+    if (!valid) return kOOB;
+    const int iy = i + (tap >> 1) + (ph >> 1) - 1, ix = j + (tap & 1) + (ph & 1) - 1;
+    if (iy < 0 || ix < 0 || iy >= p.Hin || ix >= p.Win) return kOOB;
+    return (unsigned)(((b * p.Hin + iy) * p.Win + ix) * p.Cin) * 2u + (unsigned)chunk * 16u;
+}
+
+// ... and the output row of row r = (b, i, j) of phase ph: pixel (2 i + py, 2 j + px) of sample b (returned through `b`)
+__device__ __forceinline__ int64_t up2_out_row(const GemmParams& p, int r, int ph, int& b) {
+    const int hw = p.Hin * p.Win;
+    b = r / hw;
+    const int rem = r - b * hw;
+    const int i = rem / p.Win, j = rem - i * p.Win;
+    return ((int64_t)b * p.Hout + 2 * i + (ph >> 1)) * p.Wout + 2 * j + (ph & 1);
+}
+
+// The same map for the rows mw + ro, 0 <= ro < 64, of one wave tile, without a 32-bit division per row: (b0, i0, j0) of row mw is
+// decoded once (mw is wave-uniform), and the two carries -- (j0 + ro) / Win and (i0 + carry) / Hin, dividends below 2^16 + 64 -- are
+// float products corrected by one step either way (the rounded product is within 1 of the quotient for dividends below 2^22).
+struct Up2Tile {
+    int b0, i0, j0;
+    float inv_w, inv_h;
+};
+__device__ __forceinline__ Up2Tile up2_tile(const GemmParams& p, int mw) {
+    Up2Tile t;
+    const int hw = p.Hin * p.Win;
+    t.b0 = mw / hw;
+    const int rem = mw - t.b0 * hw;
+    t.i0 = rem / p.Win;
+    t.j0 = rem - t.i0 * p.Win;
+    t.inv_w = 1.0f / (float)p.Win;
+    t.inv_h = 1.0f / (float)p.Hin;
+    return t;
+}
+__device__ __forceinline__ int up2_small_div(int n, int d, float inv) {
+    int q = (int)((float)n * inv);
+    if (q * d > n) --q;
+    if ((q + 1) * d <= n) ++q;
+    return q;
+}
+__device__ __forceinline__ int64_t up2_tile_row(const GemmParams& p, const Up2Tile& t, int ro, int ph, int& b) {
+    const int n = t.j0 + ro, cj = up2_small_div(n, p.Win, t.inv_w);
+    const int j = n - cj * p.Win;
+    const int n2 = t.i0 + cj, ci = up2_small_div(n2, p.Hin, t.inv_h);
+    const int i = n2 - ci * p.Hin;
+    b = t.b0 + ci;
+    return ((int64_t)b * p.Hout + 2 * i + (ph >> 1)) * p.Wout + 2 * j + (ph & 1);
+}
+
 template <int N> __device__ __forceinline__ void wait_vmcnt() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory"); }
 
 // hipFuncSetAttribute(MaxDynamicSharedMemorySize) is a per-(function, device) property: remember it per device, so a

@@ -67,6 +67,8 @@ SIGNATURES = {
     "gmd_ff_geglu_fused": [P, P, P, P, P, P, P, I, L, I, P],
     "gmd_conv3x3": [P, P, P, I, I, I, I, I, I, I, I, I, I, P, P, L, P, F, P, I, P, L, P],
     "gmd_conv3x3_tail": [P, P, P, P, I, I, I, I, I, I, I, L, I, I, I, I, P, P, L, P, F, P, I, P, L, P],
+    "gmd_conv3x3_up2_plan": [I, I, I, I, I, I, I, L, P],
+    "gmd_conv3x3_up2": [P, P, P, I, I, I, I, I, I, I, P, P, L, P, P, I, P, L, P],
     "gmd_conv3x3_gn_fusable": [I, I, I, I, I, I, I, I, I, I, L],
     "gmd_conv3x3_groupnorm": [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, L, P, F, I, F, P, P, I, P, L, P],
     "gmd_attention": [P, P, P, P, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P],

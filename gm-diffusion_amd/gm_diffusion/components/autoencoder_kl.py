@@ -185,6 +185,9 @@ class AutoencoderKL(_HipModule):
             e = dict(res=[resnet(f"decoder.up_blocks.{i}.resnets.{j}") for j in range(c.layers_per_block + 1)])
             if i != len(rev) - 1:
                 e["us"] = self._conv3(f"decoder.up_blocks.{i}.upsamplers.0.conv")
+                # the four 2x2 phase weights of hip_ops.conv3x3_up2, packed once; the nine-tap weight stays for the fallback
+                if ops.USE_UPSAMPLE_PHASES and ops.is_half(self._dtype) and e["us"][0].shape[1] % (9 * 64) == 0:
+                    e["us4"] = ops.pack_upsample_phases(e["us"][0])[0]
             w["d_up"].append(e)
         w["d_norm"] = self._norm("decoder.conv_norm_out")
         # conv_out: 3 output channels padded to 4 so the image is [B, HW, 4] (16-byte pixels in float32)
@@ -268,7 +271,10 @@ class AutoencoderKL(_HipModule):
             for r in blk["res"]:
                 x = self._resnet(r, x, B, H, W)
             if "us" in blk:
-                x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], upsample=True)
+                if "us4" in blk and ops.upsample_phases_ok(self._dtype, B, H, W, x.shape[-1], blk["us4"].shape[1]):
+                    x, H, W = ops.conv3x3_up2(x, blk["us4"], B, H, W, bias=blk["us"][1])
+                else:
+                    x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], upsample=True)
         x = ops.groupnorm(x, B, c.norm_num_groups, w["d_norm"][0], w["d_norm"][1], 1e-6, silu=True)
         y, _, _ = ops.conv3x3(x, w["d_out"][0], B, H, W, bias=w["d_out"][1], out_dtype=torch.float32)
         return y, H, W

@@ -535,6 +535,10 @@ class UNet2DConditionModel(_HipModule):
                 e["attn"] = [transformer(f"up_blocks.{i}.attentions.{j}", blk["heads"], blk["depth"]) for j in range(len(blk["res"]))]
             if blk["up"]:
                 e["us"] = self._conv3(f"up_blocks.{i}.upsamplers.0.conv")
+                # the four 2x2 phase weights of the exact-2x launch (hip_ops.conv3x3_up2), packed once; the nine-tap weight stays for
+                # the sizes 2H - 1, the plans without a phase loader and GMD_UPSAMPLE_PHASES=0
+                if ops.USE_UPSAMPLE_PHASES and ops.is_half(self._dtype) and e["us"][0].shape[1] % (9 * 64) == 0:
+                    e["us4"] = ops.pack_upsample_phases(e["us"][0])[0]
             w["up"].append(e)
         w["norm_out"] = self._norm("conv_norm_out")
         w["conv_out"] = self._conv3("conv_out")
@@ -893,7 +897,11 @@ class UNet2DConditionModel(_HipModule):
                 # down_block_res_samples[-1].shape[2:]): 2H x 2W -- then the very launch of upsample=True -- unless the stride-2
                 # convolution on the way down halved an odd side
                 ho, wo = skips[-1][1:]
-                x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], out_size=(ho, wo), colstats=self._wants_colstats(ho, wo))
+                cs = self._wants_colstats(ho, wo)
+                if "us4" in blk and ops.upsample_phases_ok(self._dtype, B, H, W, x.shape[-1], blk["us4"].shape[1], (ho, wo), colstats=cs):
+                    x, H, W = ops.conv3x3_up2(x, blk["us4"], B, H, W, bias=blk["us"][1], colstats=cs)
+                else:
+                    x, H, W = ops.conv3x3(x, blk["us"][0], B, H, W, bias=blk["us"][1], out_size=(ho, wo), colstats=cs)
             mark()  # end of an up block
         x = ops.groupnorm(x, B, c.norm_num_groups, w["norm_out"][0], w["norm_out"][1], eps, silu=True, split_out=self._sa(w["conv_out"][0]))
         y, _, _ = ops.conv3x3(x, w["conv_out"][0], B, H, W, bias=w["conv_out"][1], out_dtype=torch.float32)

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "conv3x3_up2", "pack_upsample_phases", "upsample_phases_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
     "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -635,6 +635,113 @@ def conv3x3_tail(x, x2, w, B, H, W, bias=None, rowbias=None, residual=None, out_
     if st is not None:
         y._colstats = (st, cout)
     return y, H, W
+
+
+# Upsample2D (nearest 2x, then conv3x3) as four 2x2 phase convolutions over the low-resolution image (gmd_conv3x3_up2): output pixel
+# (2i + py, 2j + px) reads only a 2x2 window of source pixels, so the nine taps collapse to four whose weights are sums of the taps
+# that hit the same source pixel -- K = 4 Cin instead of 9 Cin.  GMD_UPSAMPLE_PHASES=0 keeps the nine-tap launches (A/B runs, tests).
+USE_UPSAMPLE_PHASES = os.environ.get("GMD_UPSAMPLE_PHASES", "1") != "0"
+upsample_phase_uses = 0  # phase launches issued (tests assert the path is really taken)
+_PHASE_TAPS = (((0,), (1, 2)), ((0, 1), (2,)))  # [phase bit][a] -> the nine-tap indices that read source offset a + phase bit - 1
+
+
+def pack_upsample_phases(w, bias=None):
+    """(``[4, Cout, 4*Cin]`` phase weights, bias) for ``conv3x3_up2`` from the nine-tap ``w`` = [Cout, 9*Cin] (tap-major).  Phase
+    ``z = 2*py + px``; inside a phase tap ``(a, b)`` (tap-major, ``2*a + b``) reads source pixel ``(i + a + py - 1, j + b + px - 1)`` and
+    holds the sum of the nine-tap weights ``(ky, kx)`` that read that pixel: py = 0: a = 0 <- ky 0, a = 1 <- ky 1 + 2; py = 1: a = 0 <-
+    ky 0 + 1, a = 1 <- ky 2; the same in x.  Sums are formed in float32 (a wider ``w`` in its own type) and rounded ONCE to ``w.dtype``."""
+    if w.dim() != 2 or w.shape[1] % 9:
+        raise HipExtensionError(f"pack_upsample_phases: w {tuple(w.shape)} is not [Cout, 9*Cin]")
+    if getattr(w, "_split", False) or getattr(w, "_alpha", 1.0) != 1.0:
+        raise HipExtensionError("pack_upsample_phases: plain (unscaled, unsplit) weights only")
+    co, ci = w.shape[0], w.shape[1] // 9
+    w9 = w.to(torch.float32 if is_half(w.dtype) else w.dtype).view(co, 3, 3, ci)
+    out = torch.empty((4, co, 4, ci), dtype=w9.dtype, device=w.device)
+    for py in range(2):
+        for px in range(2):
+            for a in range(2):
+                for b in range(2):
+                    out[2 * py + px, :, 2 * a + b] = sum(w9[:, ky, kx] for ky in _PHASE_TAPS[py][a] for kx in _PHASE_TAPS[px][b])
+    return out.view(4, co, 4 * ci).to(w.dtype).contiguous(), (None if bias is None else _f32(bias, "bias"))
+
+
+def _up2_plan(dtype, B, H, W, cin, cout, bucket):
+    import ctypes
+
+    out = (ctypes.c_int * 4)()
+    ok = lib().gmd_conv3x3_up2_plan(dtype_code(dtype), B, H, W, cin, cout, bucket, WORKSPACE_BYTES, ctypes.addressof(out))
+    return tuple(out) if ok else None
+
+
+def upsample_phases_plan(dtype, B, H, W, cin, cout, colstats=False):
+    """(tile rows, tile columns, kernel code, K slices) of the phase launch, or None where there is none (tests, tools)."""
+    return _up2_plan(dtype, B, H, W, cin, cout, COLSTATS_BUCKET if colstats else 0) if is_half(dtype) else None
+
+
+def _up2_statistics(dtype, B, H, W, cin, cout, colstats):
+    """None: no phase launch; else whether it emits column statistics.  A nine-tap launch that WOULD emit the statistics asked for
+    keeps the launch when the phase form cannot (the next GroupNorm would need its own statistics pass)."""
+    if not is_half(dtype) or cin % 64:
+        return None
+    if colstats and USE_COLSTATS and cout % COLSTATS_BUCKET == 0 and (4 * B * H * W) % 64 == 0:
+        if _up2_plan(dtype, B, H, W, cin, cout, COLSTATS_BUCKET) is not None:
+            return True
+        if lib().gmd_gemm_colstats_plan(dtype_code(dtype), 4 * B * H * W, cout, 9 * cin, 1, WORKSPACE_BYTES, COLSTATS_BUCKET):
+            return None
+    return False if _up2_plan(dtype, B, H, W, cin, cout, 0) is not None else None
+
+
+def upsample_phases_ok(dtype, B, H, W, cin, cout, out_size=None, colstats=False):
+    """Does ``conv3x3_up2`` of these dimensions launch?  16-bit dtype, output exactly (2H, 2W) (``out_size`` None = that), Cin a
+    multiple of 64, H*W a multiple of 64 when statistics are wanted (``colstats``) and would otherwise come out of the nine-tap
+    launch, and the 256-row ping-pong plan (code 283) for the phase GEMM under the calling thread's plan family."""
+    if not USE_UPSAMPLE_PHASES or (out_size is not None and (int(out_size[0]), int(out_size[1])) != (2 * H, 2 * W)):
+        return False
+    return _up2_statistics(dtype, B, H, W, cin, cout, colstats) is not None
+
+
+def conv3x3_up2(x, wp, B, H, W, bias=None, rowbias=None, residual=None, out_dtype=None, colstats=False, out=None):
+    """``conv3x3(x, w, upsample=True)`` from the phase weights ``wp = pack_upsample_phases(w)[0]``: x [B, H*W, Cin] -> ([B, 4*H*W, Cout],
+    2H, 2W).  ``out``: a contiguous tensor of that shape to store into (tests).  Raises where ``upsample_phases_ok`` is false."""
+    global upsample_phase_uses
+    _dev(x, wp, bias, residual)
+    rb_ptr, rb_ld = _rowbias(rowbias)
+    cin = x.shape[-1]
+    if wp.dim() != 3 or wp.shape[0] != 4 or wp.shape[2] != 4 * cin or x.numel() != B * H * W * cin or x.dtype != wp.dtype or not wp.is_contiguous():
+        raise HipExtensionError(f"conv3x3_up2: shape/dtype mismatch x={tuple(x.shape)} wp={tuple(wp.shape)} B,H,W={B},{H},{W}")
+    if getattr(wp, "_split", False) or is_asplit(x):
+        raise HipExtensionError("conv3x3_up2: plain operands only")
+    cout = wp.shape[1]
+    out_dtype = out_dtype or x.dtype
+    ho, wo = 2 * H, 2 * W
+    if out is None:
+        y = torch.empty((B, ho * wo, cout), dtype=out_dtype, device=x.device)
+    else:
+        _dev(out)
+        if out.shape != (B, ho * wo, cout) or out.dtype != out_dtype or not out.is_contiguous():
+            raise HipExtensionError(f"conv3x3_up2: out {tuple(out.shape)} {out.dtype} is not a contiguous [{B}, {ho * wo}, {cout}] {out_dtype}")
+        y = out
+    if residual is not None and (residual.numel() != y.numel() or residual.dtype != x.dtype):
+        raise HipExtensionError("conv3x3_up2: residual shape/dtype mismatch")
+    if rowbias is not None and (rowbias[0] if isinstance(rowbias, tuple) else rowbias).shape[0] != B:
+        raise HipExtensionError("conv3x3_up2: rowbias must have one row per sample")
+    ws = _workspace(x.device)
+    st = None
+    if out_dtype == x.dtype and _up2_statistics(x.dtype, B, H, W, cin, cout, colstats):
+        st = torch.empty((B * ho * wo // 64, cout // COLSTATS_BUCKET, 2), dtype=torch.float32, device=x.device)
+    tm = profiling.active()
+    tm = tm if tm is not None and tm.wants("conv3x3") else None
+    t0 = tm.begin() if tm else None
+    check(lib().gmd_conv3x3_up2(_ptr(x), _ptr(wp), _ptr(y), dtype_code(x.dtype), dtype_code(out_dtype), B, H, W, cin, cout,
+                                _ptr(_f32(bias, "bias")), rb_ptr, rb_ld, _ptr(residual), _ptr(st), COLSTATS_BUCKET if st is not None else 0,
+                                _ptr(ws), WORKSPACE_BYTES, _stream()), "gmd_conv3x3_up2")
+    if tm:  # the products the launch performs: 4 taps per output pixel
+        tm.end("conv3x3", 2.0 * B * ho * wo * cout * 4 * cin, x.numel() * x.element_size() + wp.numel() * wp.element_size()
+               + y.numel() * y.element_size(), t0)
+    upsample_phase_uses += 1
+    if st is not None:
+        y._colstats = (st, cout)
+    return y, ho, wo
 
 
 USE_CONV_GN_FUSION = os.environ.get("GMD_CONV_GN", "1") != "0"  # (the switch: A/B measurements only)

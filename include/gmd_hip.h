@@ -505,6 +505,25 @@ int gmd_conv3x3_tail(const void* X, const void* X2, const void* Wt, void* Y, int
                      float* colstats, int colstats_bucket,
                      void* workspace, int64_t workspace_bytes, gmd_stream_t stream);
 
+/* gmd_conv3x3 of the nearest-2x upsampled image (upsample = 1, Hout = 2 Hin, Wout = 2 Win) as FOUR 2x2 PHASE CONVOLUTIONS over the
+ * low-resolution image (added within ABI v14: two new entry points, no signature changed).  Output pixel (2i + py, 2j + px) reads
+ * only the 2x2 window of source pixels (i + a + py - 1, j + b + px - 1), a, b in {0, 1}: the nine taps collapse to four whose
+ * weights are sums of the taps that hit the same source pixel -- py = 0: {W[ky=0], W[ky=1] + W[ky=2]}, py = 1: {W[ky=0] + W[ky=1],
+ * W[ky=2]}, the same in x -- so K = 4 Cin instead of 9 Cin.  Wp: [4][Cout][4 Cin], phase 2 py + px, tap-major (a, b) inside a phase,
+ * summed in float32 and rounded once (the caller packs it once per model).  Zero padding is that of the nine-tap form.  One launch
+ * covers the four phases; Y, bias, rowbias ([B, ldrb]), residual, column statistics (blocks of a sample contiguous, B * 4 Hin Win / 64
+ * of them as for gmd_conv3x3), out_dtype and workspace as gmd_conv3x3 (alpha = 1).  Only the 256-row ping-pong kernel has the phase
+ * loader: gmd_conv3x3_up2_plan answers 1 (and out4 = {256, 160 | 128, 283, K slices}, out4 may be NULL) exactly where the launch is
+ * taken -- 16-bit dtype, Cin % 64 == 0, that plan under the calling thread's plan family for M = 4 ceil(B Hin Win / 256) 256,
+ * K = 4 Cin, and with colstats_bucket > 0 also Hin Win % 64 == 0 and whole buckets per 80- / 64-column wave tile; otherwise
+ * gmd_conv3x3_up2 returns GMD_ERR_UNSUPPORTED and the caller issues gmd_conv3x3(.., upsample = 1, ..) with the nine-tap weight. */
+int gmd_conv3x3_up2_plan(int dtype, int B, int Hin, int Win, int Cin, int Cout, int colstats_bucket, int64_t workspace_bytes, int* out4);
+int gmd_conv3x3_up2(const void* X, const void* Wp, void* Y, int dtype, int out_dtype,
+                    int B, int Hin, int Win, int Cin, int Cout,
+                    const float* bias, const float* rowbias, int64_t ldrb, const void* residual,
+                    float* colstats, int colstats_bucket,
+                    void* workspace, int64_t workspace_bytes, gmd_stream_t stream);
+
 /* conv3x3 whose output goes straight into a GroupNorm (+SiLU): ResnetBlock2D's conv1 -> (+ time embedding) -> norm2 -> SiLU
  * (diffusers ResnetBlock2D.forward; reached through UNet2DConditionModel at stable_diffusion_dual_unet.py:1052, 1083).  On the
  * 16x16 / 8x8 UNet levels the convolution runs split-K (float32 partial slabs in `workspace`); here the GroupNorm kernel sums
