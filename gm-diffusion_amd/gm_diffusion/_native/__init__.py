@@ -84,6 +84,8 @@ SIGNATURES = {
     "gmd_timestep_embedding": [P, P, I, I, I, I, F, P],
     "gmd_timestep_embedding_add": [P, P, P, I, I, I, I, F, P],
     "gmd_concat_channels": [P, I, P, I, P, I, L, P],
+    "gmd_concat_channels_add": [P, I, P, I, P, I, P, I, P, L, P, I, L, P, I, P],
+    "gmd_silu": [P, I, L, P],
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
     "gmd_cast": [P, I, P, I, L, P],
     "gmd_dup_batch": [P, P, L, P],

@@ -11,9 +11,10 @@ from .image_processor import StableDiffusionPipelineOutput, VaeImageProcessor, r
 from .schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler, EulerDiscreteScheduler,
                          LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UniPCMultistepScheduler)
 from .unet_2d_condition import UNet2DConditionModel
+from .controlnet import ControlNetModel
 
 __all__ = [
-    "AutoencoderKL", "UNet2DConditionModel", "CLIPTextModel", "PNDMScheduler", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "EulerDiscreteScheduler",
+    "AutoencoderKL", "UNet2DConditionModel", "ControlNetModel", "CLIPTextModel", "PNDMScheduler", "DDPMScheduler", "DDIMScheduler", "DPMSolverMultistepScheduler", "EulerDiscreteScheduler",
     "EulerAncestralDiscreteScheduler", "LMSDiscreteScheduler", "LCMScheduler", "UniPCMultistepScheduler", "VaeImageProcessor",
     "StableDiffusionPipelineOutput", "randn_tensor", "FrozenDict", "ConfigMixin",
 ]

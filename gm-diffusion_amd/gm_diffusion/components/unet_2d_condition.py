@@ -442,9 +442,11 @@ class UNet2DConditionModel(_HipModule):
     # ------------------------------------------------------------------------------------------
     # weight preparation
     # ------------------------------------------------------------------------------------------
-    def _prepare(self):
+    def _prepare_encoder(self, w):
+        """conv_in, the time embedding, the down blocks and the mid block in kernel layouts, into ``w``: the half of the network a
+        ControlNet shares with its UNet (components/controlnet.py prepares its copy with this very code).  Returns the builders and the
+        running lists of the fused time-embedding projection, so that the caller can go on (the UNet: with its up blocks)."""
         c = self.config
-        w = {}
         self._cin_pad = _pad_to(c.in_channels, self._kmul())
         w["conv_in"] = self._conv3("conv_in", self._cin_pad)
         w["te1"] = self._lin("time_embedding.linear_1")
@@ -510,14 +512,7 @@ class UNet2DConditionModel(_HipModule):
                 t["blocks"].append(blk)
             return t
 
-        downs, ups = self._layout()
-        if c.addition_embed_type == "text_time":
-            wa = self._raw["add_embedding.linear_1.weight"]  # K = pooled text width + 6 sinusoids: zero-padded to the kernels' K multiple
-            self._add_k = _pad_to(wa.shape[1], self._kmul())
-            wp = torch.zeros(wa.shape[0], self._add_k)
-            wp[:, : wa.shape[1]] = wa
-            w["add1"] = (self._wt(wp), self._f32(self._raw["add_embedding.linear_1.bias"]))
-            w["add2"] = self._lin("add_embedding.linear_2")
+        downs, _ = self._layout()
         w["down"] = []
         for i, blk in enumerate(downs):
             e = dict(res=[resnet(f"down_blocks.{i}.resnets.{j}") for j in range(len(blk["res"]))])
@@ -528,6 +523,20 @@ class UNet2DConditionModel(_HipModule):
             w["down"].append(e)
         w["mid"] = dict(r0=resnet("mid_block.resnets.0"), a=transformer("mid_block.attentions.0", downs[-1]["heads"], downs[-1]["depth"]),
                         r1=resnet("mid_block.resnets.1"))
+        return resnet, transformer, te_w, te_b
+
+    def _prepare(self):
+        c = self.config
+        w = {}
+        resnet, transformer, te_w, te_b = self._prepare_encoder(w)
+        _, ups = self._layout()
+        if c.addition_embed_type == "text_time":
+            wa = self._raw["add_embedding.linear_1.weight"]  # K = pooled text width + 6 sinusoids: zero-padded to the kernels' K multiple
+            self._add_k = _pad_to(wa.shape[1], self._kmul())
+            wp = torch.zeros(wa.shape[0], self._add_k)
+            wp[:, : wa.shape[1]] = wa
+            w["add1"] = (self._wt(wp), self._f32(self._raw["add_embedding.linear_1.bias"]))
+            w["add2"] = self._lin("add_embedding.linear_2")
         w["up"] = []
         for i, blk in enumerate(ups):
             e = dict(res=[resnet(f"up_blocks.{i}.resnets.{j}") for j in range(len(blk["res"]))])
@@ -820,10 +829,65 @@ class UNet2DConditionModel(_HipModule):
         ent["src"] = cond  # keep the source alive while the key is valid
         return ent["buf"]
 
+    def _time_embedding(self, w, B):
+        """The fused time-embedding projection of this forward: float32 [B, sum(Cout)] (every ResnetBlock2D's ``time_emb_proj`` of
+        ``silu(time_embedding(t))`` in one GEMM), from the timestep in ``_t_dev``."""
+        c = self.config
+        if c.time_cond_proj_dim is None:
+            te = ops.timestep_embedding(self._t_dev, B, c.block_out_channels[0], self._dtype, c.flip_sin_to_cos, c.freq_shift)
+        else:  # t_emb.to(dtype) + cond_proj(timestep_cond) in ONE launch, as the plain embedding; zeros until set_timestep_cond
+            te = ops.timestep_embedding_add(self._t_dev, self._tcond_entry(B)["buf"], B, c.block_out_channels[0], self._dtype,
+                                            c.flip_sin_to_cos, c.freq_shift)
+        te = ops.gemm_nt(te, w["te1"][0], bias=w["te1"][1], act=ops.ACT_SILU)
+        aug = None
+        if c.addition_embed_type == "text_time":  # emb = time_embedding(t) + add_embedding(...): the sum goes through the SiLU below
+            ent = self._aug.get(B)
+            if ent is None:
+                raise HipExtensionError("this UNet needs its added conditioning first: set_added_cond(added_cond_kwargs, batch)")
+            aug = ent["aug"]
+        temb = ops.gemm_nt(te, w["te2"][0], bias=w["te2"][1], residual=aug, act=ops.ACT_SILU)  # = silu(temb): the only use of temb
+        return ops.gemm_nt(temb, w["te_all"][0], bias=w["te_all"][1], out_dtype=torch.float32)  # [B, sum(Cout)] f32
+
+    def _down_mid(self, w, x, B, Bc, H, W, temb, ehs, mark, cond=None):
+        """conv_in, the down blocks and the mid block on the packed input: the walk a ControlNet shares with its UNet.  ``Bc``: rows
+        carried at the start (B / 2 under the CFG shared prefix); ``cond``: a tensor added to conv_in's output in its epilogue (the
+        ControlNet's conditioning embedding; None for the UNet: the plain launch).  Returns (x, skips, H, W) with
+        ``skips`` = [(tensor, h, w)] in the order diffusers collects ``down_block_res_samples``."""
+        eps = self.config.norm_eps
+        x, _, _ = ops.conv3x3(x, w["conv_in"][0], Bc, H, W, bias=w["conv_in"][1], residual=cond, colstats=self._wants_colstats(H, W))
+        skips = [(x, H, W)]
+        for blk in w["down"]:
+            for j, r in enumerate(blk["res"]):
+                x = self._resnet(r, x, Bc, H, W, temb[:Bc], eps)  # (both halves share the timestep: temb rows are identical)
+                if "attn" in blk:
+                    dup = Bc != B
+                    x = self._transformer(blk["attn"][j], x, Bc, H, W, ehs, cfg_dup=dup)
+                    if dup:
+                        skips = [(self._dup_batch(s_), h_, w_) for s_, h_, w_ in skips]
+                        Bc = B
+                skips.append((x, H, W))
+            if "ds" in blk:
+                x, H, W = ops.conv3x3(x, blk["ds"][0], B, H, W, bias=blk["ds"][1], stride=2,
+                                      colstats=self._wants_colstats((H + 1) // 2, (W + 1) // 2))  # stride 2, padding 1: ceil
+                skips.append((x, H, W))
+            mark()  # end of a down block
+        x = self._resnet(w["mid"]["r0"], x, B, H, W, temb, eps)
+        x = self._transformer(w["mid"]["a"], x, B, H, W, ehs)
+        x = self._resnet(w["mid"]["r1"], x, B, H, W, temb, eps)
+        mark()  # end of the mid block
+        return x, skips, H, W
+
     @_in_own_f32_mode
-    def forward_packed(self, x, B, H, W, encoder_hidden_states, cfg_shared=False):
+    def forward_packed(self, x, B, H, W, encoder_hidden_states, cfg_shared=False, control=None):
         """x: packed channels-last input [B, H*W, cin_pad]; the timestep must already be in ``_t_dev``.
         Returns float32 eps [B, out_channels, H, W].  Stream-ordered, allocation via torch only.
+
+        ``control``: None, or the ControlNet residuals ``(down, mid, scales, skip_samples)``: ``down`` twelve channels-last tensors
+        [Br, h*w, C] in the order of the skips, ``mid`` [Br, h*w, C] of the mid block's output, all UNSCALED and in the UNet dtype;
+        ``scales`` the float32 device array of thirteen factors (hip_ops.CONTROL_RESIDUALS; index 12 is the mid residual's);
+        ``skip_samples`` = B - Br leading samples that get no residual (guess mode: the unconditional half; the kernel's ``r_row0`` is
+        that many samples' rows at each level).  Each residual is added where its skip is read: ``concat_channels`` in front of an
+        up-block resnet becomes ``concat_channels_add``, the first one also carrying the mid residual.  None: today's launches.
 
         ``cfg_shared``: classifier-free guidance evaluates the SAME latents twice and only the text conditioning differs
         (stable_diffusion_dual_unet.py:1045-1047 ``torch.cat([latents] * 2)``).  Nothing before the first cross-attention
@@ -850,46 +914,25 @@ class UNet2DConditionModel(_HipModule):
             raise HipExtensionError("encoder_hidden_states must already be in the UNet dtype (use prepare_context)")
         if cfg_shared and (B % 2 or not self.supports_cfg_shared()):
             raise HipExtensionError("cfg_shared needs an even batch and a transformer in the first down block")
-        if c.time_cond_proj_dim is None:
-            te = ops.timestep_embedding(self._t_dev, B, c.block_out_channels[0], self._dtype, c.flip_sin_to_cos, c.freq_shift)
-        else:  # t_emb.to(dtype) + cond_proj(timestep_cond) in ONE launch, as the plain embedding; zeros until set_timestep_cond
-            te = ops.timestep_embedding_add(self._t_dev, self._tcond_entry(B)["buf"], B, c.block_out_channels[0], self._dtype,
-                                            c.flip_sin_to_cos, c.freq_shift)
-        te = ops.gemm_nt(te, w["te1"][0], bias=w["te1"][1], act=ops.ACT_SILU)
-        aug = None
-        if c.addition_embed_type == "text_time":  # emb = time_embedding(t) + add_embedding(...): the sum goes through the SiLU below
-            ent = self._aug.get(B)
-            if ent is None:
-                raise HipExtensionError("this UNet needs its added conditioning first: set_added_cond(added_cond_kwargs, batch)")
-            aug = ent["aug"]
-        temb = ops.gemm_nt(te, w["te2"][0], bias=w["te2"][1], residual=aug, act=ops.ACT_SILU)  # = silu(temb): the only use of temb
-        temb = ops.gemm_nt(temb, w["te_all"][0], bias=w["te_all"][1], out_dtype=torch.float32)  # [B, sum(Cout)] f32
+        temb = self._time_embedding(w, B)
         Bc = B // 2 if cfg_shared else B  # rows currently carried (the unique half until the first cross-attention)
-        x, _, _ = ops.conv3x3(x, w["conv_in"][0], Bc, H, W, bias=w["conv_in"][1], colstats=self._wants_colstats(H, W))
-        skips = [(x, H, W)]
-        for blk in w["down"]:
-            for j, r in enumerate(blk["res"]):
-                x = self._resnet(r, x, Bc, H, W, temb[:Bc], eps)  # (both halves share the timestep: temb rows are identical)
-                if "attn" in blk:
-                    dup = Bc != B
-                    x = self._transformer(blk["attn"][j], x, Bc, H, W, ehs, cfg_dup=dup)
-                    if dup:
-                        skips = [(self._dup_batch(s_), h_, w_) for s_, h_, w_ in skips]
-                        Bc = B
-                skips.append((x, H, W))
-            if "ds" in blk:
-                x, H, W = ops.conv3x3(x, blk["ds"][0], B, H, W, bias=blk["ds"][1], stride=2,
-                                      colstats=self._wants_colstats((H + 1) // 2, (W + 1) // 2))  # stride 2, padding 1: ceil
-                skips.append((x, H, W))
-            mark()  # end of a down block
-        x = self._resnet(w["mid"]["r0"], x, B, H, W, temb, eps)
-        x = self._transformer(w["mid"]["a"], x, B, H, W, ehs)
-        x = self._resnet(w["mid"]["r1"], x, B, H, W, temb, eps)
-        mark()  # end of the mid block
+        x, skips, H, W = self._down_mid(w, x, B, Bc, H, W, temb, ehs, mark)
+        if control is not None:
+            c_down, c_mid, c_scales, c_skip = control
+            if len(c_down) != len(skips) or len(skips) + 1 != ops.CONTROL_RESIDUALS:
+                raise HipExtensionError(f"control: {len(c_down)} down residuals for {len(skips)} skips (the fused concat indexes "
+                                        f"{ops.CONTROL_RESIDUALS} scales: twelve skips and the mid block)")
         for blk in w["up"]:
             for j, r in enumerate(blk["res"]):
                 s, _, _ = skips.pop()
-                x = self._resnet(r, ops.concat_channels(x, s), B, H, W, temb, eps)
+                if control is None:
+                    xs = ops.concat_channels(x, s)
+                else:  # skip + residual where the skip is read; the mid residual rides on x in the first of them (used once)
+                    k = len(skips)
+                    xs = ops.concat_channels_add(x, s, ra=c_mid, rb=c_down[k], ia=ops.CONTROL_RESIDUALS - 1, ib=k, scales=c_scales,
+                                                 r_row0=c_skip * H * W, hw=H * W if self._wants_colstats(H, W) else None)
+                    c_mid = None
+                x = self._resnet(r, xs, B, H, W, temb, eps)
                 if "attn" in blk:
                     x = self._transformer(blk["attn"][j], x, B, H, W, ehs)
             if "us" in blk:
@@ -910,14 +953,16 @@ class UNet2DConditionModel(_HipModule):
         return out
 
     @_in_own_f32_mode
-    def graphed_forward(self, B, H, W, ehs, cfg_shared=False, co_run=False):
+    def graphed_forward(self, B, H, W, ehs, cfg_shared=False, co_run=False, control=None):
         """Capture ``forward_packed`` for this (batch, latent size) into a HIP graph (one per shape, cached).
         ``co_run``: the replays share the chip with another stream's forward (the dual-UNet pipeline's two streams): the launches are
         captured under the co-running plan family (``hip_ops.plan_family``, gmd_gemm_plan_family) -- a separate cache entry.
         Returns an object with ``.x`` (static packed-input buffer: fill it with ``pack_input(..., out=g.x)``) and
         ``.replay()`` -> float32 eps [B, out_channels, H, W] (static output buffer).  The timestep is read from the
         device scalar written by ``set_timestep``; the text conditioning from the in-place K / V^T buffers written by
-        ``update_context`` -- both outside the graph, so one capture serves every step and every prompt."""
+        ``update_context`` -- both outside the graph, so one capture serves every step and every prompt.
+        ``control`` (see forward_packed): the graph reads the ControlNet's static residual buffers and the device array of scales, so
+        the key gains their identity; None is today's key and today's graph."""
         self._ensure()
         self.update_context(ehs)
         if self.config.addition_embed_type is not None and B not in self._aug:
@@ -925,6 +970,8 @@ class UNet2DConditionModel(_HipModule):
         if self.config.time_cond_proj_dim is not None:
             self._tcond_entry(B)  # exists (zeros unless set_timestep_cond wrote it) before the capture reads it
         key = (B, H, W, tuple(ehs.shape), bool(cfg_shared), bool(co_run))
+        if control is not None:
+            key += (tuple(t.data_ptr() for t in control[0]) + (control[1].data_ptr(), control[2].data_ptr(), int(control[3])),)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -935,12 +982,13 @@ class UNet2DConditionModel(_HipModule):
         g = _GraphedForward()
         g.x = torch.empty((B // 2 if cfg_shared else B, H * W, self._cin_pad), dtype=self._dtype, device=self._device)
         g.x.zero_()
+        g.control = control  # the captured launches read these buffers: alive as long as the graph
         cur = torch.cuda.current_stream(self._device)
         side = torch.cuda.Stream(device=self._device)
         side.wait_stream(cur)
         with torch.cuda.stream(side), ops.plan_family(co_run):  # warm-up on a side stream: one-time attribute calls, workspaces, allocator pools
             for _ in range(2):
-                self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared)
+                self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control)
         cur.wait_stream(side)
         torch.cuda.synchronize(self._device)
         g.graph = torch.cuda.CUDAGraph()
@@ -948,7 +996,7 @@ class UNet2DConditionModel(_HipModule):
         self._capturing = True
         try:
             with ops.capture_in_flight(), ops.workspace_scope(g.ws), ops.plan_family(co_run), torch.cuda.graph(g.graph):
-                g.out = self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared)
+                g.out = self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control)
         finally:
             self._capturing = False
         while len(self._graphs) >= self.max_cached_graphs:  # oldest first: a graph pins its activations pool and 96 MB of scratch
@@ -989,9 +1037,27 @@ class UNet2DConditionModel(_HipModule):
         div = tuple(div) if isinstance(div, (tuple, list)) else (div, 1.0)
         return ops.pack_unet_input(a.contiguous(), None if b is None else b.contiguous(), dup, self._cin_pad, self._dtype, out=out, div=div)
 
+    def _control_from_nchw(self, down, mid, B):
+        """diffusers' ``down_block_additional_residuals`` / ``mid_block_additional_residual`` (NCHW, already scaled by the ControlNet)
+        as the ``control`` of forward_packed: channels-last in the UNet dtype, every scale 1 (``s + r * 1`` is ``s + r``)."""
+        if down is None or mid is None:
+            raise ValueError("down_block_additional_residuals and mid_block_additional_residual must be given together")
+
+        def cl(t):
+            if not torch.is_tensor(t) or t.dim() != 4 or t.shape[0] != B or not t.is_cuda:
+                raise ValueError(f"additional residuals must be device tensors [B={B}, C, h, w]")
+            t = t.permute(0, 2, 3, 1).reshape(B, t.shape[2] * t.shape[3], t.shape[1]).contiguous()
+            if t.dtype != self._dtype:
+                t = ops.cast(t if t.dtype in (torch.float32, torch.bfloat16, torch.float16) else t.float(), self._dtype)
+            return t
+
+        ones = torch.ones(ops.CONTROL_RESIDUALS, dtype=torch.float32, device=self._device)
+        return ([cl(t) for t in down], cl(mid), ones, 0)
+
     @_in_own_f32_mode
     def __call__(self, sample, timestep, encoder_hidden_states=None, timestep_cond=None, cross_attention_kwargs=None,
-                 added_cond_kwargs=None, return_dict=True, **kwargs):
+                 added_cond_kwargs=None, down_block_additional_residuals=None, mid_block_additional_residual=None,
+                 return_dict=True, **kwargs):
         if timestep_cond is not None and self.config.time_cond_proj_dim is None:
             raise ValueError("timestep_cond was given, but this UNet has no time_embedding.cond_proj: its config key "
                              "time_cond_proj_dim is None")
@@ -1006,7 +1072,11 @@ class UNet2DConditionModel(_HipModule):
         self.set_added_cond(added_cond_kwargs, B)
         if self.config.time_cond_proj_dim is not None:
             self.set_timestep_cond(None if timestep_cond is None else timestep_cond.to(self._device), B)
-        out = self.forward_packed(x, B, H, W, ehs)
+        if down_block_additional_residuals is None and mid_block_additional_residual is None:
+            out = self.forward_packed(x, B, H, W, ehs)
+        else:
+            out = self.forward_packed(x, B, H, W, ehs, control=self._control_from_nchw(down_block_additional_residuals,
+                                                                                     mid_block_additional_residual, B))
         if not return_dict:
             return (out,)
         from .image_processor import UNetOutput

@@ -25,7 +25,7 @@ from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GM
 __all__ = [
     "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "conv3x3_up2", "pack_upsample_phases", "upsample_phases_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
-    "concat_channels", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
+    "concat_channels", "concat_channels_add", "silu_", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
 ]
 
@@ -1001,6 +1001,76 @@ def concat_channels(a, b):
     if sa is not None and sb is not None and not isinstance(sa, list) and not isinstance(sb, list):
         out._colstats = [sa, sb]  # a following GroupNorm reads the two producers' statistics side by side
     return out
+
+
+# ControlNet residuals are added where the up blocks read their skips anyway (gmd_concat_channels_add).  The skip producer's column
+# statistics are WRONG for the sum, so they are never forwarded: the result carries none and the following GroupNorm takes its general
+# route.  The launch CAN leave fresh statistics of the stored B part (the GroupNorm then stays one-pass), but as measured that does not
+# pay: the statistics pass costs 13-42 us per concat on the 64x64 / 32x32 levels and saves 8-12 us in the GroupNorm, +0.5 ... +0.9 % on the
+# whole ControlNet step (profiles/controlnet.txt).  So it is OFF by default; GMD_CONCAT_STATS=1 switches it on (A/B measurements, tests).
+CONTROL_RESIDUALS = 13  # an SD-1.5 ControlNet: twelve down-block residuals and the mid-block residual
+USE_CONCAT_STATS = os.environ.get("GMD_CONCAT_STATS", "0") == "1"
+CONCAT_STATS_MAX_CB = 4096  # the statistics pass keeps 16 bytes of LDS per B-part channel
+
+
+def concat_channels_add(a, b, ra=None, rb=None, ia=0, ib=0, scales=None, r_row0=0, hw=None):
+    """``cat([a + ra * scales[ia], b + rb * scales[ib]], -1)`` over channels-last rows, each sum rounded as torch rounds
+    ``s + r * scale`` (gmd_concat_channels_add).  ``ra`` / ``rb``: residuals of the rows from ``r_row0`` on, or None (that part is a
+    copy); ``scales``: float32 device tensor of CONTROL_RESIDUALS entries, read by the kernel.  ``hw``: rows per sample -- given, and with
+    USE_CONCAT_STATS on, the launch leaves fresh column statistics of the B part for the following GroupNorm (``out._colstats``).  A
+    part that a residual modified never passes its producer's statistics on."""
+    _dev(a, b, ra, rb, scales)
+    ca, cb = a.shape[-1], b.shape[-1]
+    rows = a.numel() // ca
+    if b.numel() // cb != rows or a.dtype != b.dtype:
+        raise HipExtensionError("concat_channels_add: row count / dtype mismatch")
+    r_row0 = int(r_row0)
+    if not 0 <= r_row0 <= rows:
+        raise HipExtensionError(f"concat_channels_add: r_row0={r_row0} outside [0, {rows}]")
+    for r, c, i, nm in ((ra, ca, ia, "ra"), (rb, cb, ib, "rb")):
+        if r is None:
+            continue
+        if r.dtype != a.dtype or r.shape[-1] != c or r.numel() != (rows - r_row0) * c:
+            raise HipExtensionError(f"concat_channels_add: {nm} must hold {rows - r_row0} rows of {c} channels of {a.dtype} "
+                                    f"(got {tuple(r.shape)} of {r.dtype})")
+        if not 0 <= int(i) < CONTROL_RESIDUALS:
+            raise HipExtensionError(f"concat_channels_add: scale index {i} outside [0, {CONTROL_RESIDUALS})")
+    if ra is not None or rb is not None:
+        if scales is None or scales.dtype != torch.float32 or scales.numel() != CONTROL_RESIDUALS:
+            raise HipExtensionError(f"concat_channels_add: scales must be a float32 device tensor of {CONTROL_RESIDUALS} entries")
+    out = torch.empty(a.shape[:-1] + (ca + cb,), dtype=a.dtype, device=a.device)
+    sa = None if ra is not None else getattr(a, "_colstats", None)
+    sb = None if rb is not None else getattr(b, "_colstats", None)
+    if isinstance(sa, list):
+        sa = None
+    if isinstance(sb, list):
+        sb = None
+    st = None
+    if (rb is not None and sa is not None and USE_CONCAT_STATS and USE_COLSTATS and hw and hw % 64 == 0 and rows % hw == 0
+            and cb % COLSTATS_BUCKET == 0 and cb <= CONCAT_STATS_MAX_CB):
+        st = torch.empty((rows // 64, cb // COLSTATS_BUCKET, 2), dtype=torch.float32, device=a.device)
+        sb = (st, cb)
+    tm, t0 = _timed("concat")
+    check(lib().gmd_concat_channels_add(_ptr(a), ca, _ptr(ra), int(ia), _ptr(b), cb, _ptr(rb), int(ib), _ptr(scales), r_row0, _ptr(out),
+                                        dtype_code(a.dtype), rows, _ptr(st), COLSTATS_BUCKET if st is not None else 0, _stream()),
+          "gmd_concat_channels_add")
+    if tm:
+        extra = sum(r.numel() for r in (ra, rb) if r is not None)
+        tm.end("concat", 0.0, (2 * out.numel() + extra) * out.element_size(), t0)
+    if sa is not None and sb is not None:
+        out._colstats = [sa, sb]  # both parts' statistics describe what was stored: side by side, as concat_channels leaves them
+    return out
+
+
+def silu_(x):
+    """``x * sigmoid(x)`` in place (gmd_silu: the formula of the GroupNorm + SiLU kernels); returns ``x``."""
+    _dev(x)
+    if is_asplit(x):
+        raise HipExtensionError("silu_: the input is a pre-split activation (only contractions read that layout)")
+    check(lib().gmd_silu(_ptr(x), dtype_code(x.dtype), x.numel(), _stream()), "gmd_silu")
+    if getattr(x, "_colstats", None) is not None:  # the statistics described the values before the activation
+        del x._colstats
+    return x
 
 
 _SIDE_STREAMS = {}

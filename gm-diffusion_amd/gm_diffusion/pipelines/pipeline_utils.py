@@ -14,7 +14,7 @@ import os
 
 import torch
 
-from ..components import (AutoencoderKL, CLIPTextModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
+from ..components import (AutoencoderKL, CLIPTextModel, ControlNetModel, DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
                           EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, PNDMScheduler, UNet2DConditionModel,
                           UniPCMultistepScheduler)
 from ..components.configuration import FrozenDict
@@ -22,6 +22,7 @@ from ..components.configuration import FrozenDict
 _LOADABLE = {
     "UNet2DConditionModel": UNet2DConditionModel,
     "AutoencoderKL": AutoencoderKL,
+    "ControlNetModel": ControlNetModel,
     "CLIPTextModel": CLIPTextModel,  # model_index.json lists it under "transformers": the HIP implementation takes over
     "PNDMScheduler": PNDMScheduler,
     "DDPMScheduler": DDPMScheduler,

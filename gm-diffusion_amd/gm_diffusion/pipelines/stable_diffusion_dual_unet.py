@@ -55,6 +55,12 @@ Guidance-embedded (LCM) UNets (config ``time_cond_proj_dim``; :1024-1030): the S
 as ``timestep_cond`` and runs without the CFG duplicate.  The reference hands that one tensor, of the SDR UNet's width, to BOTH UNets
 (:1056, :1088), which only works when both have the same ``time_cond_proj_dim``.  Here the GM UNet gets an embedding of its own
 width if and only if it has ``time_cond_proj_dim`` itself, and none otherwise: equal to the reference where the reference runs.
+
+ControlNet (the reference README's "ControlNet-conditioned HDR generation", which it gets from diffusers): the constructor keyword
+``controlnet=`` takes a ``components.ControlNetModel`` and ``__call__`` then reads diffusers' ``control_image``,
+``controlnet_conditioning_scale``, ``guess_mode``, ``control_guidance_start`` / ``control_guidance_end``.  Only the SDR UNet is steered;
+the GM UNet follows the SDR x0.  Fused path: inside the guidance window a step replays the ControlNet's graph and then the UNet's control
+graph on the SDR stream, outside it the plain UNet graph; the scale lives in device memory, so no value of it needs a new capture.
 """
 from __future__ import annotations
 
@@ -80,10 +86,54 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
     co_run_plans = None
     _step_probe = None  # test hook: callable(i, sdr_latents, gm_latents) after every loop iteration
 
+    _optional_components = ["safety_checker", "feature_extractor", "image_encoder", "controlnet"]
+
     def __init__(self, vae, text_encoder, tokenizer, unet, gm_unet, scheduler, safety_checker, feature_extractor,
-                 image_encoder=None, requires_safety_checker: bool = True):
+                 image_encoder=None, requires_safety_checker: bool = True, controlnet=None):
+        if isinstance(controlnet, (list, tuple)):
+            raise NotImplementedError("a list of ControlNets (diffusers' MultiControlNetModel) is not implemented: pass one ControlNetModel")
         self._init_common(vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor, image_encoder,
-                          requires_safety_checker, gm_unet=gm_unet)
+                          requires_safety_checker, gm_unet=gm_unet, controlnet=controlnet)
+
+    # ---- ControlNet conditioning of the SDR UNet (the GM UNet follows the SDR x0 and is never conditioned) -------------------------
+    def _prepare_control_image(self, image, height, width, rows, device):
+        """diffusers' control-image preparation as far as it applies here: float32 NCHW in [0, 1] (no normalisation) of exactly
+        ``height`` x ``width``, one image per latent row (a single image serves every row).  Tensors [B, 3, H, W] / [3, H, W] in
+        [0, 1], uint8 arrays [H, W, 3] / [B, H, W, 3] and PIL images are taken; a wrong size is an error, not a resize."""
+        if image is None:
+            raise ValueError("this pipeline has a controlnet: `control_image` is required")
+        if isinstance(image, (list, tuple)):
+            if len(image) == 0:
+                raise ValueError("`control_image` is an empty list")
+            image = [self._prepare_control_image(im, height, width, 1, "cpu") for im in image]
+            image = torch.cat(image, 0)
+        elif not torch.is_tensor(image):
+            import numpy as np
+
+            arr = np.asarray(image)
+            if arr.ndim == 2:
+                arr = np.stack([arr] * 3, -1)
+            if arr.ndim == 3:
+                arr = arr[None]
+            if arr.ndim != 4 or arr.shape[-1] != 3:
+                raise ValueError(f"`control_image` must be an RGB image; got an array of shape {arr.shape}")
+            t = torch.from_numpy(np.ascontiguousarray(arr)).permute(0, 3, 1, 2)
+            image = t.float() / 255.0 if t.dtype == torch.uint8 else t.float()
+        if image.dim() == 3:
+            image = image[None]
+        if image.dim() != 4 or tuple(image.shape[-2:]) != (height, width):
+            raise ValueError(f"`control_image` must be {height} x {width} (height x width of this call); got {tuple(image.shape)}")
+        if image.shape[0] == 1 and rows > 1:
+            image = image.expand(rows, -1, -1, -1)
+        if image.shape[0] != rows:
+            raise ValueError(f"`control_image` holds {image.shape[0]} images for {rows} latents")
+        return image.to(device=device, dtype=torch.float32).contiguous()
+
+    @staticmethod
+    def _control_keep(n, start, end):
+        from ..components.controlnet import control_window
+
+        return [control_window(i, n, start, end) for i in range(n)]
 
     @staticmethod
     def _batched_added_cond(added_cond, do_cfg, device):
@@ -155,6 +205,20 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         else:
             batch_size = prompt_embeds.shape[0]
         device = self._execution_device
+        # ControlNet conditioning of the SDR UNet (diffusers' StableDiffusionControlNetPipeline keywords).  Without a controlnet the
+        # five keywords stay in **kwargs and are ignored, as every unknown keyword is.
+        cn = getattr(self, "controlnet", None)
+        if cn is not None:
+            cn_scale = kwargs.pop("controlnet_conditioning_scale", 1.0)
+            guess_mode = bool(kwargs.pop("guess_mode", False))
+            cg_start, cg_end = kwargs.pop("control_guidance_start", 0.0), kwargs.pop("control_guidance_end", 1.0)
+            if any(isinstance(v, (list, tuple)) for v in (cn_scale, cg_start, cg_end)):
+                raise NotImplementedError("per-ControlNet lists of scales / guidance windows belong to Multi-ControlNet, which is not implemented")
+            cn_scale, cg_start, cg_end = float(cn_scale), float(cg_start), float(cg_end)
+            if cg_start >= cg_end or cg_start < 0.0 or cg_end > 1.0:
+                raise ValueError(f"control guidance window [{cg_start}, {cg_end}] must satisfy 0 <= start < end <= 1")
+            control_image = self._prepare_control_image(kwargs.pop("control_image", None), height, width,
+                                                        batch_size * num_images_per_prompt, "cpu")
         lora_scale = self.cross_attention_kwargs.get("scale", None) if self.cross_attention_kwargs is not None else None
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, device, num_images_per_prompt, self.do_classifier_free_guidance, negative_prompt,
@@ -185,6 +249,17 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
 
         sdr_added, gm_added = self._batched_added_cond(added_cond, do_cfg, latents.device)
         fused = self._use_fused(latents, self.unet, self.scheduler) and self._use_fused(latents, self.gm_unet, self.gm_scheduler)
+        keep = None  # per step: does the ControlNet run (diffusers' control guidance window); None without a controlnet
+        if cn is not None:
+            keep = self._control_keep(len(timesteps), cg_start, cg_end)
+            cn_half = guess_mode and do_cfg  # guess mode: the ControlNet sees the conditional half only
+            control_image = control_image.to(latents.device)
+            if do_cfg and not cn_half:
+                control_image = torch.cat([control_image] * 2)
+            cn_embeds = prompt_embeds[n_neg:] if cn_half else prompt_embeds
+            if fused and (cn.dtype != self.unet.dtype or cn.device != self.unet.device):
+                raise ValueError(f"the controlnet ({cn.dtype} on {cn.device}) must share the SDR UNet's dtype and device "
+                                 f"({self.unet.dtype} on {self.unet.device}): its residuals are added in the UNet's own kernels")
         if fused:
             ctx = self.unet.prepare_context(prompt_embeds)
             gm_ctx = self.gm_unet.prepare_context(gm_prompt_embeds)
@@ -208,8 +283,23 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             # product; -2.2 % per batch against the launch-by-launch plans, +8.6 % if the streams were serialised:
             # profiles/r05_ab_plan_default.txt), a single-stream run keeps the plans that are fastest alone
             co_run = (gm_stream is not sdr_stream) if self.co_run_plans is None else bool(self.co_run_plans)
+            g_cn = g_sdr_c = control = None
+            if cn is not None:
+                # constant over the loop, written once outside any graph: the conditioning embedding and the thirteen scales.  The
+                # ControlNet runs on the SDR stream in front of the UNet that reads its residuals; it has no CFG shared prefix, so it
+                # takes the duplicated batch (or, in guess mode, the conditional half: the UNet then skips the unconditional samples)
+                cn_rows = latents.shape[0] if cn_half else nb_sdr
+                cn_ctx = cn.prepare_context(cn_embeds)
+                cn.set_condition(control_image, cn_rows)
+                cn_scales = cn.set_scales(cn_scale, guess_mode)
+                cn_skip = nb_sdr - cn_rows
             if self._graphs_ok():
-                g_sdr = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run)
+                if cn is None or not all(keep):
+                    g_sdr = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run)
+                if cn is not None and any(keep):
+                    g_cn = cn.graphed_forward(cn_rows, h, w, cn_ctx, co_run=co_run)
+                    control = (g_cn.down, g_cn.mid, cn_scales, cn_skip)
+                    g_sdr_c = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run, control=control)
                 g_gm = self.gm_unet.graphed_forward(latents.shape[0], h, w, gm_ctx, co_run=co_run)
             pre = self._predraw_step_noise([self.scheduler, self.gm_scheduler], ts_host, latents.shape, generator, latents.device,
                                            eta=extra_step_kwargs.get("eta", 0.0))
@@ -230,11 +320,24 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     continue
                 if fused:
                     div = self._pack_div(self.scheduler, ts_host[i])
-                    x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_sdr.x if g_sdr else None,
+                    use_cn = cn is not None and keep[i]  # inside the control guidance window: ControlNet, then the UNet's control graph
+                    g_step = g_sdr_c if use_cn else g_sdr
+                    x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_step.x if g_step else None,
                                              **({"div": (div, 1.0)} if div is not None else {}))
                     self.unet.set_timestep_from(ts_dev, i)
-                    if g_sdr:
-                        sdr_noise_pred = g_sdr.replay()
+                    if use_cn:  # the same latents and timestep, packed for the ControlNet's own batch
+                        cx = cn.pack_input(latents, dup=2 if (do_cfg and not cn_half) else 1, out=g_cn.x if g_cn else None,
+                                           **({"div": (div, 1.0)} if div is not None else {}))
+                        cn.set_timestep_from(ts_dev, i)
+                    if g_step:
+                        if use_cn:
+                            g_cn.replay()
+                        sdr_noise_pred = g_step.replay()
+                    elif use_cn:
+                        with ops.plan_family(co_run):
+                            c_down, c_mid = cn.forward_packed(cx, cn_rows, h, w, cn_ctx)
+                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared,
+                                                                      control=(c_down, c_mid, cn_scales, cn_skip))
                     else:
                         with ops.plan_family(co_run):
                             sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared)
@@ -262,9 +365,20 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
                     latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
                     gm_latents = self.gm_scheduler.scale_model_input(gm_latents, t)
+                    cn_kw = {}
+                    if cn is not None and keep[i]:
+                        # diffusers' StableDiffusionControlNetPipeline: guess mode infers the conditional half only and pads the
+                        # unconditional half's residuals with zeros
+                        c_in = self.scheduler.scale_model_input(latents, t) if cn_half else latent_model_input
+                        c_down, c_mid = cn(c_in, t, cn_embeds, controlnet_cond=control_image, conditioning_scale=cn_scale,
+                                           guess_mode=guess_mode, return_dict=False)
+                        if cn_half:
+                            c_down = [torch.cat([torch.zeros_like(d), d]) for d in c_down]
+                            c_mid = torch.cat([torch.zeros_like(c_mid), c_mid])
+                        cn_kw = dict(down_block_additional_residuals=c_down, mid_block_additional_residual=c_mid)
                     sdr_noise_pred = self.unet(latent_model_input, t, encoder_hidden_states=prompt_embeds, timestep_cond=timestep_cond,
                                                cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=sdr_added,
-                                               return_dict=False)[0]
+                                               return_dict=False, **cn_kw)[0]
                     if do_cfg:
                         sdr_noise_pred_uncond, sdr_noise_pred_text = sdr_noise_pred.chunk(2)
                         sdr_noise_pred = sdr_noise_pred_uncond + self.guidance_scale * (sdr_noise_pred_text - sdr_noise_pred_uncond)

@@ -610,6 +610,25 @@ int gmd_timestep_embedding_add(const float* t_dev, const void* addend, void* out
 /* out[r, :Ca] = A[r], out[r, Ca:] = Bm[r]  (skip-connection concat, channels-last) */
 int gmd_concat_channels(const void* A, int Ca, const void* Bm, int Cb, void* out, int dtype,
                         int64_t rows, gmd_stream_t stream);
+/* The skip-connection concat with ControlNet residuals added where the skip is read (added within ABI v14; csrc/controlnet.hip):
+ *   out[r, :Ca] = Ra ? rnd(A[r]  + rnd(Ra[r - r_row0] * scales[ia])) : A[r]
+ *   out[r, Ca:] = Rb ? rnd(Bm[r] + rnd(Rb[r - r_row0] * scales[ib])) : Bm[r]        (rows r < r_row0: plain copy)
+ * rnd = one rounding to `dtype`; product and sum in float32 and never contracted: bit for bit torch's `s + r * scale` on tensors of
+ * `dtype` with a float32 scalar.  Ra [rows - r_row0, Ca] / Rb [rows - r_row0, Cb] of `dtype`, either may be NULL (that part is then a
+ * copy).  scales: float32 DEVICE array of 13 entries read by the kernel (ia, ib in [0, 13)); the host rewrites it outside a captured
+ * graph.  r_row0 in [0, rows]: the residuals cover the rows from r_row0 on (guess mode: the conditional half of a guidance batch).
+ * Alignment and channel multiples as gmd_concat_channels (16-byte pointers, Ca and Cb multiples of 8 (16-bit) / 4 (float32)).
+ * colstats_b (may be NULL): the launch also writes float32 [rows/64][Cb/colstats_bucket][2] = {sum, sum of squares} of the STORED
+ * B-part outputs in a fixed order (32 + 2 + bucket float32 additions per entry, as the producers' row epilogue): the stats_b operand
+ * of gmd_groupnorm_colstats.  Needs rows % 64 == 0, Cb % colstats_bucket == 0, Cb <= 4096 (and, for the consumer, a sample's rows a
+ * multiple of 64).  Anything else returns GMD_ERR_INVALID before a launch. */
+int gmd_concat_channels_add(const void* A, int Ca, const void* Ra, int ia, const void* Bm, int Cb, const void* Rb, int ib,
+                            const float* scales, int64_t r_row0, void* out, int dtype, int64_t rows,
+                            float* colstats_b, int colstats_bucket, gmd_stream_t stream);
+/* X[i] = X[i] * sigmoid(X[i]) in place, n elements (a multiple of 8 (16-bit) / 4 (float32)), with the formula of the GroupNorm + SiLU
+ * kernels (hardware reciprocal of 1 + exp(-x), float32 inside, one rounding on the store).  The ControlNet conditioning embedding's
+ * activations, once per call (added within ABI v14). */
+int gmd_silu(void* X, int dtype, int64_t n, gmd_stream_t stream);
 /* out[r, :] = table[ids[r], :] + pos[r % T, :]  (token + position embedding of the CLIP text encoder,
  * stable_diffusion_gm.py:398-439); ids int32 in [0, vocab) -- out-of-range ids are an error the HOST must
  * exclude (checked there), rows = B*T. */

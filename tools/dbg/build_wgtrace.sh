@@ -8,8 +8,8 @@ BD=build/wgtrace_${OUT%.so}
 mkdir -p $BD
 FLAGS="-O3 -fPIC -std=c++17 --offload-arch=gfx950 -Wall -Wno-unused-function -Wno-unused-variable -DGMD_WG_TRACE=1 $*"
 pids=()
-for f in hdr_tail latent_step norm elementwise gemm gemm_split ff_fused attention attention_split; do
-  extra=""; case $f in hdr_tail|latent_step) extra="-ffp-contract=off";; esac
+for f in hdr_tail latent_step norm elementwise controlnet gemm gemm_split ff_fused attention attention_split; do
+  extra=""; case $f in hdr_tail|latent_step|controlnet) extra="-ffp-contract=off";; esac
   /opt/rocm/bin/hipcc $FLAGS $extra -c $f.hip -o $BD/$f.o &
   pids+=($!)
   if [ ${#pids[@]} -ge 4 ]; then wait ${pids[0]}; pids=("${pids[@]:1}"); fi
