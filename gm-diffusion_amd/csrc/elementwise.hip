@@ -108,6 +108,24 @@ __global__ __launch_bounds__(kThreads) void embedding_kernel(const int32_t* __re
     }
 }
 
+// out = a + b * scales[idx] on 16-byte vectors, float32 inside, one rounding on the store: the combine of the COMPOSED decoupled
+// cross-attention (two gmd_attention launches; the 16-bit types have gmd_attention_ip).  The scale is read from device memory.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void scaled_add_kernel(const T* __restrict__ A, const T* __restrict__ Bm, T* Y,
+                                                              const float* __restrict__ scales, int idx, int64_t nvec) {
+    GMD_WG_TRACE_SCOPE(WGK_OTHER);
+    constexpr int V = Elem<T>::kVec;
+    const float s = scales[idx];
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nvec; i += (int64_t)gridDim.x * blockDim.x) {
+        float a[V], b[V];
+        load_vec(A + i * V, a);
+        load_vec(Bm + i * V, b);
+#pragma unroll
+        for (int j = 0; j < V; ++j) a[j] = a[j] + b[j] * s;
+        store_vec(Y + i * V, a);
+    }
+}
+
 inline int grid_for(int64_t n) {
     int64_t g = (n + kThreads - 1) / kThreads;
     if (g > 256 * 16) g = 256 * 16;
@@ -221,6 +239,23 @@ int gmd_dup_batch(const void* in, void* out, int64_t bytes, gmd_stream_t stream)
     return GMD_OK;
 }
 
+int gmd_scaled_add(const void* A, const void* Bm, void* out, int dtype, int64_t n, const float* scales, int index, gmd_stream_t stream) {
+    GMD_REQUIRE(n >= 0, "gmd_scaled_add: negative n");
+    GMD_REQUIRE(gmd_known_dtype(dtype), "gmd_scaled_add: bad dtype %d", dtype);
+    const int cv = gmd_is_half(dtype) ? 8 : 4;
+    GMD_REQUIRE(n % cv == 0, "gmd_scaled_add: n must be a multiple of %d", cv);
+    GMD_REQUIRE(scales != nullptr && index >= 0, "gmd_scaled_add: the scale is a device array, the index non-negative");
+    if (n == 0) return GMD_OK;
+    GMD_REQUIRE(A && Bm && out && gmd_aligned16(A) && gmd_aligned16(Bm) && gmd_aligned16(out), "gmd_scaled_add: null or unaligned pointer");
+    GMD_REQUIRE(Bm != out, "gmd_scaled_add: out may alias a, not b");
+    gmd_for_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        scaled_add_kernel<T><<<grid_for(n / cv), kThreads, 0, (hipStream_t)stream>>>((const T*)A, (const T*)Bm, (T*)out, scales, index, n / cv);
+    });
+    GMD_CHECK_LAUNCH("gmd_scaled_add");
+    return GMD_OK;
+}
+
 int gmd_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, gmd_stream_t stream) {
     GMD_REQUIRE(n >= 0, "gmd_cast: negative n");
     if (n == 0) return GMD_OK;
@@ -269,12 +304,13 @@ GMD_WG_TRACE_SETTER(elementwise)
 // by capacity x 32-byte records, zeroed by the caller; nullptr switches the trace off).  Not stream-ordered: call it with the device idle.
 extern "C" int gmd_wg_trace_set_gemm(void*);
 extern "C" int gmd_wg_trace_set_attention(void*);
+extern "C" int gmd_wg_trace_set_attention_ip(void*);
 extern "C" int gmd_wg_trace_set_norm(void*);
 extern "C" int gmd_wg_trace_set_ff_fused(void*);
 extern "C" int gmd_wg_trace_set_latent_step(void*);
 extern "C" int gmd_wg_trace_set_controlnet(void*);
 extern "C" int gmd_wg_trace_enable(void* ring) {
-    return gmd_wg_trace_set_gemm(ring) | gmd_wg_trace_set_attention(ring) | gmd_wg_trace_set_norm(ring) | gmd_wg_trace_set_ff_fused(ring) |
+    return gmd_wg_trace_set_gemm(ring) | gmd_wg_trace_set_attention(ring) | gmd_wg_trace_set_attention_ip(ring) | gmd_wg_trace_set_norm(ring) | gmd_wg_trace_set_ff_fused(ring) |
            gmd_wg_trace_set_latent_step(ring) | gmd_wg_trace_set_elementwise(ring) | gmd_wg_trace_set_controlnet(ring);
 }
 #endif

@@ -72,6 +72,7 @@ SIGNATURES = {
     "gmd_conv3x3_gn_fusable": [I, I, I, I, I, I, I, I, I, I, L],
     "gmd_conv3x3_groupnorm": [P, P, P, P, I, I, I, I, I, I, I, I, I, P, P, L, P, F, I, F, P, P, I, P, L, P],
     "gmd_attention": [P, P, P, P, I, I, I, I, I, I, L, L, L, L, L, L, L, L, F, I, P],
+    "gmd_attention_ip": [P, P, P, P, P, P, I, I, I, I, I, I, I, L, L, L, L, L, L, L, L, L, L, L, L, F, P, I, P],
     "gmd_softmax_rows": [P, L, P, I, L, L, I, F, I, P],
     "gmd_groupnorm_nsplit": [L],
     "gmd_groupnorm_stats": [P, I, I, L, I, I, F, P, P, P, P, P],
@@ -87,6 +88,7 @@ SIGNATURES = {
     "gmd_concat_channels_add": [P, I, P, I, P, I, P, I, P, L, P, I, L, P, I, P],
     "gmd_silu": [P, I, L, P],
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
+    "gmd_scaled_add": [P, P, P, I, L, P, I, P],
     "gmd_cast": [P, I, P, I, L, P],
     "gmd_dup_batch": [P, P, L, P],
 }

@@ -246,6 +246,14 @@ class _GraphedForward:
         return self.out
 
 
+class _IPContext:
+    """An image prompt prepared by ``UNet2DConditionModel.prepare_ip_context``: the row count and the number of image keys select the
+    persistent K_ip / V_ip^T buffers the cross-attentions read; ``tokens`` [rows, Nip, cross_dim] are the projected IP tokens."""
+
+    def __init__(self, rows, nip, tokens, owner):
+        self.rows, self.nip, self.tokens, self.owner = rows, nip, tokens, owner
+
+
 class UNet2DConditionModel(_HipModule):
     config_name = "config.json"
     max_cached_graphs = 8  # captured forwards kept per model (one per batch / latent size / token count)
@@ -277,6 +285,12 @@ class UNet2DConditionModel(_HipModule):
         self._graphs = {}
         self._aug = {}  # text_time conditioning: persistent [B, temb] buffers, rewritten in place by set_added_cond
         self._tcond = {}  # time_cond_proj_dim: persistent [B, ch0] buffers of cond_proj(timestep_cond), rewritten in place by set_timestep_cond
+        self._ip_raw = None       # IP-Adapter: CPU float32 weights (load_ip_adapter), None when no adapter is loaded
+        self._ip_w = None         # ... the same in kernel layouts, built on first use (_ensure_ip) for the prepared weights `_ip_w_of`
+        self._ip_w_of = None
+        self._ip_kv = {}          # ... persistent K_ip / V_ip^T per (layer, rows, Nip, dtype), rewritten in place by prepare_ip_context
+        self._ip_scale = 1.0      # ... set_ip_adapter_scale
+        self._ip_last = None      # ... (key of the embeddings, their context, the embeddings) of the latest prepare_ip_context
 
     # ------------------------------------------------------------------------------------------
     # structure
@@ -650,6 +664,214 @@ class UNet2DConditionModel(_HipModule):
         for t in self._transformers:
             self._cross_kv(t, ehs)
 
+    # ------------------------------------------------------------------------------------------
+    # IP-Adapter (image prompt): diffusers' load_ip_adapter / IPAdapterAttnProcessor / ImageProjection, restated
+    # ------------------------------------------------------------------------------------------
+    def _ip_layer_table(self):
+        """[(k, transformer-block key, inner dim)] of an adapter's ``{k}.to_k_ip`` / ``{k}.to_v_ip`` weights: one odd k per ``attn2``, in
+        diffusers' ``attn_processors`` order -- down blocks, then up blocks, then the mid block; the ``attn1`` processors hold the
+        even numbers.  Host arithmetic on the config only."""
+        downs, ups = self._layout()
+        rows = []
+        for name, blocks in (("down_blocks", downs), ("up_blocks", ups)):
+            for i, blk in enumerate(blocks):
+                if blk["attn"]:
+                    rows += [(f"{name}.{i}.attentions.{j}.transformer_blocks.{n}", blk["c"]) for j in range(len(blk["res"])) for n in range(blk["depth"])]
+        rows += [(f"mid_block.attentions.0.transformer_blocks.{n}", downs[-1]["c"]) for n in range(downs[-1]["depth"])]
+        return [(2 * i + 1, key, c) for i, (key, c) in enumerate(rows)]
+
+    def ip_adapter_layers(self):
+        """[(k, transformer-block key)]: which block the weights stored under number k belong to (see _ip_layer_table)."""
+        return [(k, key) for k, key, _ in self._ip_layer_table()]
+
+    def ip_adapter_expected_keys(self, tokens, clip_dim):
+        """({image_proj key: shape}, {ip_adapter key: shape}) of a plain IP-Adapter with ``tokens`` image tokens per picture."""
+        cross = self.config.cross_attention_dim
+        proj = {"proj.weight": (tokens * cross, clip_dim), "proj.bias": (tokens * cross,), "norm.weight": (cross,), "norm.bias": (cross,)}
+        kv = {}
+        for k, _, c in self._ip_layer_table():
+            kv[f"{k}.to_k_ip.weight"] = (c, cross)
+            kv[f"{k}.to_v_ip.weight"] = (c, cross)
+        return proj, kv
+
+    def load_ip_adapter(self, state_dict):
+        """Install a plain IP-Adapter: ``state_dict`` = {"image_proj": {...}, "ip_adapter": {...}} as diffusers reads it.
+        ``image_proj``: ``proj.weight`` [T*cross_dim, clip_dim], ``proj.bias``, ``norm.weight``, ``norm.bias`` (ImageProjection: linear,
+        reshape to T tokens, LayerNorm eps 1e-5); ``ip_adapter``: ``{k}.to_k_ip.weight`` / ``{k}.to_v_ip.weight`` [inner_dim, cross_dim]
+        for the odd k of ip_adapter_layers().  Host work only; the device copies are made at the first prepare_ip_context."""
+        if self._ip_raw is not None:
+            raise NotImplementedError("an IP-Adapter is already loaded: several adapters at once are not implemented "
+                                      "(unload_ip_adapter() first)")
+        if not isinstance(state_dict, dict) or "image_proj" not in state_dict or "ip_adapter" not in state_dict:
+            raise ValueError("load_ip_adapter expects {'image_proj': {...}, 'ip_adapter': {...}}")
+        proj, kv = state_dict["image_proj"], state_dict["ip_adapter"]
+        for k in proj:
+            if "perceiver_resampler" in k:
+                raise NotImplementedError(f"IP-Adapter FaceID (image_proj key {k!r}: perceiver_resampler) is not implemented")
+            if "latents" in k:
+                raise NotImplementedError(f"IP-Adapter Plus (image_proj key {k!r}: the Resampler's latents) is not implemented")
+            if k.startswith("proj.0.") or ".proj.0." in k:
+                raise NotImplementedError(f"IP-Adapter Full-Face (image_proj key {k!r}: the MLP projection) is not implemented")
+        for k in ("proj.weight", "proj.bias", "norm.weight", "norm.bias"):
+            if k not in proj:
+                raise KeyError(f"load_ip_adapter: image_proj.{k} is missing")
+        cross = self.config.cross_attention_dim
+        pw = proj["proj.weight"]
+        if pw.dim() != 2 or pw.shape[0] % cross or pw.shape[0] == 0:
+            raise ValueError(f"shape mismatch for image_proj.proj.weight: expected [T*{cross}, clip_dim], found {tuple(pw.shape)}")
+        tokens, clip_dim = pw.shape[0] // cross, pw.shape[1]
+        want_proj, want_kv = self.ip_adapter_expected_keys(tokens, clip_dim)
+        missing = [k for k in want_kv if k not in kv]
+        unexpected = [k for k in kv if k not in want_kv]
+        if missing or unexpected:
+            raise KeyError(f"load_ip_adapter: ip_adapter missing={missing[:5]} (+{max(len(missing) - 5, 0)}) "
+                           f"unexpected={unexpected[:5]} (+{max(len(unexpected) - 5, 0)})")
+        for part, want, got in (("image_proj", want_proj, proj), ("ip_adapter", want_kv, kv)):
+            for k, shp in want.items():
+                if tuple(got[k].shape) != tuple(shp):
+                    raise ValueError(f"shape mismatch for {part}.{k}: expected {tuple(shp)}, found {tuple(got[k].shape)}")
+        cpu = lambda t: t.detach().to("cpu", torch.float32)
+        self._ip_raw = dict(tokens=tokens, clip_dim=clip_dim, proj={k: cpu(proj[k]) for k in want_proj}, kv={k: cpu(kv[k]) for k in want_kv})
+        self._drop_ip_device_state()
+        return self
+
+    def unload_ip_adapter(self):
+        """Back to the UNet without an image prompt: the launches, and so the outputs, of a model that never had one."""
+        self._ip_raw = None
+        self._ip_scale = 1.0
+        self._drop_ip_device_state()
+        return self
+
+    def _drop_ip_device_state(self):
+        self._ip_w = self._ip_w_of = self._ip_last = None
+        self._ip_kv = {}
+        # captured forwards that read the dropped buffers (key element ("ip", rows, Nip)); the others never touched them
+        self._graphs = {k: g for k, g in self._graphs.items() if not any(isinstance(e, tuple) and e[:1] == ("ip",) for e in k)}
+
+    @property
+    def has_ip_adapter(self):
+        return self._ip_raw is not None
+
+    def set_ip_adapter_scale(self, scale):
+        """One scale for every cross-attention layer (default 1.0), written into the float32 device array the kernels read -- outside
+        any captured graph, so a captured forward serves every scale."""
+        if isinstance(scale, (list, tuple, dict)):
+            raise NotImplementedError("set_ip_adapter_scale: per-adapter lists and per-block dicts are not implemented (one float)")
+        if self._ip_raw is None:
+            raise ValueError("set_ip_adapter_scale: no IP-Adapter is loaded")
+        if self._capturing:
+            raise HipExtensionError("the IP-Adapter scale must be set outside graph capture")
+        self._ip_scale = float(scale)
+        if self._ip_w is not None and self._ip_w_of is self._w:
+            self._ip_w["scales"].copy_(torch.full((self._ip_w["scales"].numel(),), self._ip_scale, dtype=torch.float32))
+
+    def _ensure_ip(self):
+        """The adapter's weights in kernel layouts, next to (and for) the prepared UNet weights."""
+        self._ensure()
+        if self._ip_raw is None:
+            raise ValueError("this UNet has no IP-Adapter: call load_ip_adapter() first (image_embeds given)")
+        if self._ip_w is not None and self._ip_w_of is self._w:
+            return self._ip_w
+        if self._capturing:
+            raise HipExtensionError("the IP-Adapter must be prepared (prepare_ip_context) before graph capture")
+        raw = self._ip_raw
+        kpad = _pad_to(raw["clip_dim"], self._kmul())  # K = clip_dim: zero-padded to the kernels' K multiple
+        wp = torch.zeros(raw["proj"]["proj.weight"].shape[0], kpad)
+        wp[:, : raw["clip_dim"]] = raw["proj"]["proj.weight"]
+        layers = self.ip_adapter_layers()
+        w = dict(proj=(self._wt(wp), self._f32(raw["proj"]["proj.bias"])), kpad=kpad,
+                 norm=(self._f32(raw["proj"]["norm.weight"]), self._f32(raw["proj"]["norm.bias"])), layers={},
+                 scales=torch.full((len(layers),), self._ip_scale, dtype=torch.float32, device=self._device))
+        for i, (k, blk) in enumerate(layers):
+            w["layers"][blk] = dict(k=self._wt(raw["kv"][f"{k}.to_k_ip.weight"]), v=self._wa(raw["kv"][f"{k}.to_v_ip.weight"]), index=i)
+        self._ip_kv = {}
+        self._ip_w, self._ip_w_of = w, self._w
+        return w
+
+    @staticmethod
+    def _single_adapter_embeds(image_embeds):
+        if isinstance(image_embeds, (list, tuple)):
+            if len(image_embeds) != 1:
+                raise NotImplementedError(f"image_embeds holds {len(image_embeds)} tensors: several IP-Adapters at once are not implemented")
+            image_embeds = image_embeds[0]
+        if not torch.is_tensor(image_embeds) or image_embeds.dim() not in (2, 3):
+            raise ValueError("image_embeds must be a tensor [rows, n_images, clip_dim] (or [rows, clip_dim])")
+        return image_embeds if image_embeds.dim() == 3 else image_embeds.unsqueeze(1)
+
+    def prepare_ip_context(self, image_embeds):
+        """image_embeds [rows, n_images, clip_dim] (rows ordered like the text rows: [negative; positive] under guidance) -> the image
+        prompt context ``forward_packed(ip=...)`` takes.  Runs ImageProjection (linear, T tokens per image, LayerNorm eps 1e-5) into
+        the IP tokens [rows, n_images*T, cross_dim], then K_ip and V_ip^T of every transformer block, exactly as _cross_kv does for
+        the text: persistent buffers per (layer, rows, Nip, dtype), rewritten in place, so a captured forward keeps reading valid
+        addresses.  Eager HIP launches, once per pipeline call."""
+        if self._ip_raw is None:
+            raise ValueError("this UNet has no IP-Adapter: call load_ip_adapter() first (image_embeds given)")
+        raw = self._ip_raw
+        if not torch.is_tensor(image_embeds) or image_embeds.dim() != 3 or image_embeds.shape[2] != raw["clip_dim"]:
+            raise ValueError(f"image_embeds must be [rows, n_images, {raw['clip_dim']}] "
+                             f"(got {tuple(image_embeds.shape) if torch.is_tensor(image_embeds) else type(image_embeds).__name__})")
+        rows, n_img, clip = image_embeds.shape
+        T = raw["tokens"]
+        nip = n_img * T
+        if nip > ops.ATTN_IP_MAX_KEYS:
+            raise ValueError(f"{n_img} images x {T} tokens = {nip} image keys: at most {ops.ATTN_IP_MAX_KEYS} (one key tile) are supported")
+        if rows == 0 or n_img == 0:
+            raise ValueError("image_embeds is empty")
+        if not image_embeds.is_cuda:
+            raise HipExtensionError("image_embeds must be on the HIP device")
+        if self._capturing:
+            raise HipExtensionError("the image prompt must be prepared (prepare_ip_context) before graph capture")
+        return self._project_ip(image_embeds)
+
+    @_in_own_f32_mode
+    def _project_ip(self, image_embeds):
+        """The device work of prepare_ip_context (its argument checks are host-only and come first)."""
+        raw = self._ip_raw
+        rows, n_img, clip = image_embeds.shape
+        T = raw["tokens"]
+        nip = n_img * T
+        w = self._ensure_ip()
+        # the same tensor again (the generic loop hands it over at every step): the buffers already hold its K_ip / V_ip^T
+        key = (image_embeds.data_ptr(), image_embeds._version, tuple(image_embeds.shape), image_embeds.dtype)
+        if self._ip_last is not None and self._ip_last[0] == key and self._ip_last[1].owner is w:
+            return self._ip_last[1]
+        cross = self.config.cross_attention_dim
+        src = image_embeds.contiguous()
+        if src.dtype != self._dtype:
+            src = ops.cast(src if src.dtype in (torch.float32, torch.bfloat16, torch.float16) else src.float(), self._dtype)
+        src = src.view(rows * n_img, clip)
+        if w["kpad"] != clip:
+            pad = torch.zeros((rows * n_img, w["kpad"]), dtype=self._dtype, device=self._device)
+            pad[:, :clip].copy_(src)
+            src = pad
+        tok = ops.gemm_nt(src, w["proj"][0], bias=w["proj"][1]).view(rows * nip, cross)
+        tok = ops.layernorm(tok, w["norm"][0], w["norm"][1], 1e-5).view(rows, nip, cross)
+        lpad = _pad_to(nip, 8 if ops.is_half(self._dtype) else 4)
+        for blk, lw in w["layers"].items():
+            C = lw["k"].shape[0]
+            slot = (blk, rows, nip, self._dtype)
+            ent = self._ip_kv.get(slot)
+            if ent is None:
+                ent = self._ip_kv[slot] = dict(kc=torch.empty((rows, nip, C), dtype=self._dtype, device=self._device),
+                                               vt=torch.zeros((rows, C, lpad), dtype=self._dtype, device=self._device))
+            ops.gemm_nt(tok.view(rows * nip, cross), lw["k"], out=ent["kc"].view(rows * nip, C))
+            ops.gemm_nt(lw["v"], tok, out=ent["vt"], ldc=lpad)
+        ctx = _IPContext(rows, nip, tok, w)
+        self._ip_last = (key, ctx, image_embeds)  # holding the tensor keeps its address from being recycled while the key is valid
+        return ctx
+
+    def _check_ip(self, ip, B):
+        if not isinstance(ip, _IPContext) or ip.owner is not self._ip_w or self._ip_w_of is not self._w:
+            raise HipExtensionError("ip: not a context of this UNet's current adapter (prepare_ip_context again after loading or moving)")
+        if ip.rows != B:
+            raise ValueError(f"the image prompt has {ip.rows} rows, the batch {B}")
+
+    def _ip_kv_of(self, t, B, ip):
+        ent = self._ip_kv.get((t["key"], B, ip.nip, self._dtype))
+        if ent is None:
+            raise HipExtensionError("IP-Adapter K/V must be prepared (prepare_ip_context) before the forward / graph capture")
+        return ent["kc"], ent["vt"], self._ip_w["layers"][t["key"]]["index"]
+
     @staticmethod
     def _dup_batch(t):
         """[B, ...] -> [2B, ...]: both halves equal to ``t`` (gmd_dup_batch: one read, two writes)."""
@@ -659,7 +881,7 @@ class UNet2DConditionModel(_HipModule):
             out._colstats = (torch.cat([st[0], st[0]], 0), st[1])
         return out
 
-    def _transformer(self, t, x, B, H, W, ehs, cfg_dup=False):
+    def _transformer(self, t, x, B, H, W, ehs, cfg_dup=False, ip=None):
         """``cfg_dup``: x holds the B UNIQUE samples of a classifier-free-guidance pair whose two halves differ only in the
         text conditioning; everything up to the first cross-attention query is computed once, then duplicated (returns 2B rows)."""
         C = x.shape[-1]
@@ -667,13 +889,15 @@ class UNet2DConditionModel(_HipModule):
         h = ops.groupnorm(x, B, self.config.norm_num_groups, t["norm"][0], t["norm"][1], 1e-6, silu=False, split_out=self._sa(t["pin"][0]))
         h = ops.gemm_nt(h.view(B * N, C), t["pin"][0], bias=t["pin"][1], a_split=ops.is_asplit(h))  # conv1x1 and nn.Linear proj_in are the same GEMM on tokens
         for blk in t["blocks"]:
-            h, x, B = self._transformer_block(blk, h, x, B, N, C, ehs, cfg_dup)
+            h, x, B = self._transformer_block(blk, h, x, B, N, C, ehs, cfg_dup, ip)
             cfg_dup = False  # the first cross-attention has duplicated the batch
         y = ops.gemm_nt(h, t["pout"][0], bias=t["pout"][1], residual=x.view(B * N, C), colstats=self._wants_colstats(H, W))
         return ops.carry_colstats(y.view(B, N, C), y)
 
-    def _transformer_block(self, t, h, x, B, N, C, ehs, cfg_dup):
-        """One BasicTransformerBlock on tokens ``h`` [B*N, C]; returns (h, x, B) -- x / B change when ``cfg_dup`` duplicates."""
+    def _transformer_block(self, t, h, x, B, N, C, ehs, cfg_dup, ip=None):
+        """One BasicTransformerBlock on tokens ``h`` [B*N, C]; returns (h, x, B) -- x / B change when ``cfg_dup`` duplicates.
+        ``ip``: None (the launches of a UNet without an adapter), or the image-prompt context of prepare_ip_context: the cross-attention
+        becomes the decoupled one, text branch + ip_scale * image branch."""
         heads = t["heads"]
         d = C // heads
         # self-attention
@@ -689,7 +913,16 @@ class UNet2DConditionModel(_HipModule):
             B *= 2
         kc, vtc = self._cross_kv(t, ehs)
         L = ehs.shape[1]
-        if ops.is_half(self._dtype) or ops.split_attention_ok(self._dtype, d):
+        if ip is not None:
+            kip, vtip, idx = self._ip_kv_of(t, B, ip)
+            if ops.is_half(self._dtype) or ops.split_attention_ok(self._dtype, d):
+                # 16-bit: one launch (gmd_attention_ip); float32 on the matrix cores: two launches and the scaled add, plain float32 out
+                o = ops.attention_ip(q, kc, vtc, kip, vtip, heads, L, ip.nip, d ** -0.5, self._ip_w["scales"], idx)
+            else:
+                o = composed_attention(q, 0, C, kc, 0, C, vtc, B, heads, d, N, L, d ** -0.5, self._dtype)
+                oi = composed_attention(q, 0, C, kip, 0, C, vtip, B, heads, d, N, ip.nip, d ** -0.5, self._dtype)
+                o = ops.scaled_add(o, oi, self._ip_w["scales"], idx, out=o)
+        elif ops.is_half(self._dtype) or ops.split_attention_ok(self._dtype, d):
             o = ops.attention(q, kc, vtc, heads, L, d ** -0.5, split_out=self._sa(t["o2"][0]))
         else:
             o = composed_attention(q, 0, C, kc, 0, C, vtc, B, heads, d, N, L, d ** -0.5, self._dtype)
@@ -848,7 +1081,7 @@ class UNet2DConditionModel(_HipModule):
         temb = ops.gemm_nt(te, w["te2"][0], bias=w["te2"][1], residual=aug, act=ops.ACT_SILU)  # = silu(temb): the only use of temb
         return ops.gemm_nt(temb, w["te_all"][0], bias=w["te_all"][1], out_dtype=torch.float32)  # [B, sum(Cout)] f32
 
-    def _down_mid(self, w, x, B, Bc, H, W, temb, ehs, mark, cond=None):
+    def _down_mid(self, w, x, B, Bc, H, W, temb, ehs, mark, cond=None, ip=None):
         """conv_in, the down blocks and the mid block on the packed input: the walk a ControlNet shares with its UNet.  ``Bc``: rows
         carried at the start (B / 2 under the CFG shared prefix); ``cond``: a tensor added to conv_in's output in its epilogue (the
         ControlNet's conditioning embedding; None for the UNet: the plain launch).  Returns (x, skips, H, W) with
@@ -861,7 +1094,7 @@ class UNet2DConditionModel(_HipModule):
                 x = self._resnet(r, x, Bc, H, W, temb[:Bc], eps)  # (both halves share the timestep: temb rows are identical)
                 if "attn" in blk:
                     dup = Bc != B
-                    x = self._transformer(blk["attn"][j], x, Bc, H, W, ehs, cfg_dup=dup)
+                    x = self._transformer(blk["attn"][j], x, Bc, H, W, ehs, cfg_dup=dup, ip=ip)
                     if dup:
                         skips = [(self._dup_batch(s_), h_, w_) for s_, h_, w_ in skips]
                         Bc = B
@@ -872,13 +1105,13 @@ class UNet2DConditionModel(_HipModule):
                 skips.append((x, H, W))
             mark()  # end of a down block
         x = self._resnet(w["mid"]["r0"], x, B, H, W, temb, eps)
-        x = self._transformer(w["mid"]["a"], x, B, H, W, ehs)
+        x = self._transformer(w["mid"]["a"], x, B, H, W, ehs, ip=ip)
         x = self._resnet(w["mid"]["r1"], x, B, H, W, temb, eps)
         mark()  # end of the mid block
         return x, skips, H, W
 
     @_in_own_f32_mode
-    def forward_packed(self, x, B, H, W, encoder_hidden_states, cfg_shared=False, control=None):
+    def forward_packed(self, x, B, H, W, encoder_hidden_states, cfg_shared=False, control=None, ip=None):
         """x: packed channels-last input [B, H*W, cin_pad]; the timestep must already be in ``_t_dev``.
         Returns float32 eps [B, out_channels, H, W].  Stream-ordered, allocation via torch only.
 
@@ -888,6 +1121,9 @@ class UNet2DConditionModel(_HipModule):
         ``skip_samples`` = B - Br leading samples that get no residual (guess mode: the unconditional half; the kernel's ``r_row0`` is
         that many samples' rows at each level).  Each residual is added where its skip is read: ``concat_channels`` in front of an
         up-block resnet becomes ``concat_channels_add``, the first one also carrying the mid residual.  None: today's launches.
+
+        ``ip``: None, or the image-prompt context of ``prepare_ip_context`` (B rows, ordered like ``encoder_hidden_states``): every
+        cross-attention adds its image branch.  None: today's launches.
 
         ``cfg_shared``: classifier-free guidance evaluates the SAME latents twice and only the text conditioning differs
         (stable_diffusion_dual_unet.py:1045-1047 ``torch.cat([latents] * 2)``).  Nothing before the first cross-attention
@@ -914,9 +1150,11 @@ class UNet2DConditionModel(_HipModule):
             raise HipExtensionError("encoder_hidden_states must already be in the UNet dtype (use prepare_context)")
         if cfg_shared and (B % 2 or not self.supports_cfg_shared()):
             raise HipExtensionError("cfg_shared needs an even batch and a transformer in the first down block")
+        if ip is not None:
+            self._check_ip(ip, B)
         temb = self._time_embedding(w, B)
         Bc = B // 2 if cfg_shared else B  # rows currently carried (the unique half until the first cross-attention)
-        x, skips, H, W = self._down_mid(w, x, B, Bc, H, W, temb, ehs, mark)
+        x, skips, H, W = self._down_mid(w, x, B, Bc, H, W, temb, ehs, mark, ip=ip)
         if control is not None:
             c_down, c_mid, c_scales, c_skip = control
             if len(c_down) != len(skips) or len(skips) + 1 != ops.CONTROL_RESIDUALS:
@@ -934,7 +1172,7 @@ class UNet2DConditionModel(_HipModule):
                     c_mid = None
                 x = self._resnet(r, xs, B, H, W, temb, eps)
                 if "attn" in blk:
-                    x = self._transformer(blk["attn"][j], x, B, H, W, ehs)
+                    x = self._transformer(blk["attn"][j], x, B, H, W, ehs, ip=ip)
             if "us" in blk:
                 # upsample to the size of the skip this level's output meets next (diffusers: upsample_size =
                 # down_block_res_samples[-1].shape[2:]): 2H x 2W -- then the very launch of upsample=True -- unless the stride-2
@@ -953,7 +1191,7 @@ class UNet2DConditionModel(_HipModule):
         return out
 
     @_in_own_f32_mode
-    def graphed_forward(self, B, H, W, ehs, cfg_shared=False, co_run=False, control=None):
+    def graphed_forward(self, B, H, W, ehs, cfg_shared=False, co_run=False, control=None, ip=None):
         """Capture ``forward_packed`` for this (batch, latent size) into a HIP graph (one per shape, cached).
         ``co_run``: the replays share the chip with another stream's forward (the dual-UNet pipeline's two streams): the launches are
         captured under the co-running plan family (``hip_ops.plan_family``, gmd_gemm_plan_family) -- a separate cache entry.
@@ -962,7 +1200,9 @@ class UNet2DConditionModel(_HipModule):
         device scalar written by ``set_timestep``; the text conditioning from the in-place K / V^T buffers written by
         ``update_context`` -- both outside the graph, so one capture serves every step and every prompt.
         ``control`` (see forward_packed): the graph reads the ControlNet's static residual buffers and the device array of scales, so
-        the key gains their identity; None is today's key and today's graph."""
+        the key gains their identity; None is today's key and today's graph.
+        ``ip`` (see forward_packed): the graph reads the persistent K_ip / V_ip^T buffers of (rows, Nip) and the device array of
+        scales, so the key gains ("ip", rows, Nip): one capture serves every image and every scale."""
         self._ensure()
         self.update_context(ehs)
         if self.config.addition_embed_type is not None and B not in self._aug:
@@ -972,6 +1212,9 @@ class UNet2DConditionModel(_HipModule):
         key = (B, H, W, tuple(ehs.shape), bool(cfg_shared), bool(co_run))
         if control is not None:
             key += (tuple(t.data_ptr() for t in control[0]) + (control[1].data_ptr(), control[2].data_ptr(), int(control[3])),)
+        if ip is not None:
+            self._check_ip(ip, B)
+            key += (("ip", ip.rows, ip.nip),)
         g = self._graphs.get(key)
         if g is not None:
             return g
@@ -988,7 +1231,7 @@ class UNet2DConditionModel(_HipModule):
         side.wait_stream(cur)
         with torch.cuda.stream(side), ops.plan_family(co_run):  # warm-up on a side stream: one-time attribute calls, workspaces, allocator pools
             for _ in range(2):
-                self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control)
+                self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control, ip=ip)
         cur.wait_stream(side)
         torch.cuda.synchronize(self._device)
         g.graph = torch.cuda.CUDAGraph()
@@ -996,7 +1239,7 @@ class UNet2DConditionModel(_HipModule):
         self._capturing = True
         try:
             with ops.capture_in_flight(), ops.workspace_scope(g.ws), ops.plan_family(co_run), torch.cuda.graph(g.graph):
-                g.out = self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control)
+                g.out = self.forward_packed(g.x, B, H, W, ehs, cfg_shared=cfg_shared, control=control, ip=ip)
         finally:
             self._capturing = False
         while len(self._graphs) >= self.max_cached_graphs:  # oldest first: a graph pins its activations pool and 96 MB of scratch
@@ -1069,14 +1312,18 @@ class UNet2DConditionModel(_HipModule):
         if ehs.shape[0] != B:
             raise ValueError(f"encoder_hidden_states batch {ehs.shape[0]} != sample batch {B}")
         self.set_timestep(timestep)
+        ip = None
+        if added_cond_kwargs and "image_embeds" in added_cond_kwargs:  # diffusers' form: a list with one tensor per adapter
+            added_cond_kwargs = dict(added_cond_kwargs)
+            ip = self.prepare_ip_context(self._single_adapter_embeds(added_cond_kwargs.pop("image_embeds")))
         self.set_added_cond(added_cond_kwargs, B)
         if self.config.time_cond_proj_dim is not None:
             self.set_timestep_cond(None if timestep_cond is None else timestep_cond.to(self._device), B)
         if down_block_additional_residuals is None and mid_block_additional_residual is None:
-            out = self.forward_packed(x, B, H, W, ehs)
+            out = self.forward_packed(x, B, H, W, ehs, ip=ip)
         else:
-            out = self.forward_packed(x, B, H, W, ehs, control=self._control_from_nchw(down_block_additional_residuals,
-                                                                                     mid_block_additional_residual, B))
+            out = self.forward_packed(x, B, H, W, ehs, ip=ip, control=self._control_from_nchw(down_block_additional_residuals,
+                                                                                            mid_block_additional_residual, B))
         if not return_dict:
             return (out,)
         from .image_processor import UNetOutput

@@ -69,6 +69,20 @@ def shard_prompt_batch(prompt_embeds, negative_prompt_embeds, latents, total_bat
     return pos[lo:hi].contiguous(), neg[lo:hi].contiguous(), latents[lo:hi].contiguous(), (lo, hi)
 
 
+def shard_image_embeds(image_embeds, lo_hi, total_batch, do_classifier_free_guidance):
+    """This rank's rows of a full-batch image prompt with one row per UNet row (what ``UNet2DConditionModel.prepare_ip_context`` and
+    ``added_cond_kwargs["image_embeds"]`` take): the ``(lo, hi)`` range that ``shard_prompt_batch`` returned for the prompts, taken
+    from the positive rows and, under guidance, from the negative rows in front of them ([negative; positive]).  (The pipelines'
+    ``ip_adapter_image_embeds`` is one [negative; positive] pair repeated for every row and needs no sharding.)"""
+    lo, hi = lo_hi
+    want = (2 if do_classifier_free_guidance else 1) * total_batch
+    if image_embeds.shape[0] != want:
+        raise ValueError(f"image_embeds has {image_embeds.shape[0]} rows, expected {want} for a batch of {total_batch}")
+    if not do_classifier_free_guidance:
+        return image_embeds[lo:hi].contiguous()
+    return torch.cat([image_embeds[lo:hi], image_embeds[total_batch + lo:total_batch + hi]]).contiguous()
+
+
 def gather_outputs(t, total_batch, group=None):
     """Gather per-rank row slices (possibly ragged) of ``t`` on rank 0; returns the full tensor there, None elsewhere."""
     if not is_dist():

@@ -23,7 +23,7 @@ from . import profiling
 from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GMD_F16, GMD_F32, GMD_F32S, GMD_F32SA, GMD_F32SW, HipExtensionError, check, lib
 
 __all__ = [
-    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "conv3x3_up2", "pack_upsample_phases", "upsample_phases_ok", "attention", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
+    "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "conv3x3_up2", "pack_upsample_phases", "upsample_phases_ok", "attention", "attention_ip", "scaled_add", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
     "concat_channels", "concat_channels_add", "silu_", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
@@ -821,6 +821,81 @@ def attention(q, k, vt, heads, nk, scale, k_col=0, causal=False, split_out=False
     if tm:  # QK^T + PV, algorithmic head dim (padding not counted)
         tm.end("attention", 4.0 * B * nq * nk * hd, (2 * B * nq * hd + 2 * B * nk * hd) * q.element_size(), t0)
     return _mark_asplit(o) if so else o
+
+
+# Decoupled cross-attention of an IP-Adapter: the 16-bit types take ONE launch (gmd_attention_ip).  GMD_ATTN_IP_FUSED=0 (read once)
+# sends them down the composed route instead -- two attention launches and scaled_add, what float32 always runs: the A/B switch.
+USE_ATTN_IP_FUSED = os.environ.get("GMD_ATTN_IP_FUSED", "1") != "0"
+ATTN_IP_MAX_KEYS = 64  # the image keys are one tile of the kernel
+
+
+def _ip_scale_arg(ip_scales, ip_index, what):
+    if ip_scales is None or ip_scales.dtype != torch.float32 or not ip_scales.is_contiguous():
+        raise HipExtensionError(f"{what}: ip_scales must be a contiguous float32 device tensor")
+    if not 0 <= int(ip_index) < ip_scales.numel():
+        raise HipExtensionError(f"{what}: scale index {ip_index} outside [0, {ip_scales.numel()})")
+    return int(ip_index)
+
+
+def scaled_add(a, b, scales, index, out=None):
+    """``a + b * scales[index]`` in float32, one rounding on the store (gmd_scaled_add); ``scales`` is a float32 device tensor read by
+    the kernel.  ``out`` may be ``a`` (in place)."""
+    _dev(a, b, scales)
+    if a.dtype != b.dtype or a.shape != b.shape or not a.is_contiguous() or not b.is_contiguous():
+        raise HipExtensionError("scaled_add: a and b must be contiguous tensors of one shape and dtype")
+    if is_asplit(a) or is_asplit(b):
+        raise HipExtensionError("scaled_add: an input is a pre-split activation (only contractions read that layout)")
+    index = _ip_scale_arg(scales, index, "scaled_add")
+    if out is None:
+        out = torch.empty_like(a)
+    elif out.dtype != a.dtype or out.shape != a.shape or not out.is_contiguous():
+        raise HipExtensionError("scaled_add: out must match a")
+    check(lib().gmd_scaled_add(_ptr(a), _ptr(b), _ptr(out), dtype_code(a.dtype), a.numel(), _ptr(scales), index, _stream()),
+          "gmd_scaled_add")
+    return out
+
+
+def attention_ip_composed(q, k, vt, kip, vtip, heads, nk, nip, scale, ip_scales, ip_index):
+    """The decoupled cross-attention as two ``attention`` launches and ``scaled_add``: float32 in F32_MODE 'split', and the baseline
+    the fused kernel is measured against (16-bit types)."""
+    index = _ip_scale_arg(ip_scales, ip_index, "attention_ip")
+    o = attention(q, k, vt, heads, nk, scale)
+    oi = attention(q, kip, vtip, heads, nip, scale)
+    return scaled_add(o, oi, ip_scales, index, out=o)
+
+
+def attention_ip(q, k, vt, kip, vtip, heads, nk, nip, scale, ip_scales, ip_index, fused=None):
+    """``softmax(scale q k^T) v + ip_scales[ip_index] * softmax(scale q kip^T) vip``: two independent softmaxes over the text keys and
+    the ``nip`` <= 64 image keys.  q: [B, Nq, ldq] and k: [B, Nk, ldk] with the heads in columns [0, H*D); vt: [B, H*D, ldvt]; kip:
+    [B, Nip, ldkip]; vtip: [B, H*D, ldvtip] (zero pad columns, as vt).  ``ip_scales``: float32
+    device tensor read by the kernel, so a captured graph serves every scale.  16-bit types: one launch (gmd_attention_ip) unless
+    ``fused`` is False (default: USE_ATTN_IP_FUSED); float32: the composed route."""
+    _dev(q, k, vt, kip, vtip, ip_scales)
+    index = _ip_scale_arg(ip_scales, ip_index, "attention_ip")
+    B, nq = q.shape[0], q.shape[1]
+    hd = vt.shape[1]
+    d = hd // heads
+    ldq, ldk = q.shape[2], k.shape[2]
+    if not 1 <= nip <= ATTN_IP_MAX_KEYS:
+        raise HipExtensionError(f"attention_ip: {nip} image keys outside [1, {ATTN_IP_MAX_KEYS}]")
+    if (k.shape[1] < nk or vt.shape[2] < nk or hd > ldk or hd > ldq or kip.shape[0] != B or kip.shape[1] < nip
+            or kip.shape[2] < hd or vtip.shape[0] != B or vtip.shape[1] != hd or vtip.shape[2] < nip or k.shape[0] != B or vt.shape[0] != B):
+        raise HipExtensionError("attention_ip: operand shapes inconsistent")
+    fused = USE_ATTN_IP_FUSED if fused is None else bool(fused)
+    if not (is_half(q.dtype) and fused):
+        return attention_ip_composed(q, k, vt, kip, vtip, heads, nk, nip, scale, ip_scales, index)
+    o = torch.empty((B, nq, hd), dtype=q.dtype, device=q.device)
+    es = q.element_size()
+    tm = profiling.active()
+    tm = tm if tm is not None and tm.wants("attention") else None
+    t0 = tm.begin() if tm else None
+    check(lib().gmd_attention_ip(_ptr(q), _ptr(k), _ptr(vt), _ptr(kip), _ptr(vtip), _ptr(o), dtype_code(q.dtype),
+                                 B, heads, d, nq, nk, nip, ldq, ldk, vt.shape[2], kip.shape[2], vtip.shape[2], hd,
+                                 nq * ldq, k.shape[1] * ldk, hd * vt.shape[2], kip.shape[1] * kip.shape[2], hd * vtip.shape[2], nq * hd,
+                                 float(scale), _ptr(ip_scales), index, _stream()), "gmd_attention_ip")
+    if tm:  # both branches' QK^T + PV; Q and O move once
+        tm.end("attention", 4.0 * B * nq * (nk + nip) * hd, (2 * B * nq * hd + 2 * B * (nk + nip) * hd) * es, t0)
+    return o
 
 
 def softmax_rows(s, cols, scale, out_dtype, ldp=None, causal_nq=0):

@@ -16,8 +16,9 @@
 #     See the License for the specific language governing permissions and
 #     limitations under the License.
 #
-# Changes from that text: the LoRA / textual-inversion / IP-adapter branches are removed, the denoising loop, latent step,
-# UNet / VAE calls and the decode tail are new (hand-written HIP kernels behind gm_diffusion.hip_ops).
+# Changes from that text: the LoRA / textual-inversion branches are removed, the IP-adapter branch keeps the plain adapter only, the
+# denoising loop, latent step, UNet / VAE calls and the decode tail are new (hand-written HIP kernels behind gm_diffusion.hip_ops; see
+# DESIGN.md).
 """
 ``StableDiffusionDualUNetPipeline`` -- the Stage-3 text->HDR path: an SDR UNet (with
 classifier-free guidance) and a GM UNet (conditional only, fed the SDR x0-prediction) are stepped
@@ -61,6 +62,14 @@ ControlNet (the reference README's "ControlNet-conditioned HDR generation", whic
 ``controlnet_conditioning_scale``, ``guess_mode``, ``control_guidance_start`` / ``control_guidance_end``.  Only the SDR UNet is steered;
 the GM UNet follows the SDR x0.  Fused path: inside the guidance window a step replays the ControlNet's graph and then the UNet's control
 graph on the SDR stream, outside it the plain UNet graph; the scale lives in device memory, so no value of it needs a new capture.
+
+IP-Adapter (:518-585, :986-1020, :1058): ``load_ip_adapter`` installs a plain adapter (4 image tokens per picture) from local files,
+``ip_adapter_image`` / ``ip_adapter_image_embeds`` are prepared as in the reference ([negative; positive] rows, zeros as the negative
+image embedding) and every cross-attention of the SDR UNet becomes the decoupled one (one launch, gmd_attention_ip).  The reference
+hands the same ``added_cond_kwargs`` to both UNets (:1058, :1090), which only runs when both carry an adapter; here the GM UNet gets
+the positive rows if and only if an adapter was loaded into it (``pipe.gm_unet.load_ip_adapter``).  The scale lives in device memory:
+``set_ip_adapter_scale`` between two calls needs no new capture.  Plus / FaceID variants, several adapters, ``ip_adapter_masks`` and
+per-block scales are refused by name.
 """
 from __future__ import annotations
 
@@ -128,6 +137,122 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         if image.shape[0] != rows:
             raise ValueError(f"`control_image` holds {image.shape[0]} images for {rows} latents")
         return image.to(device=device, dtype=torch.float32).contiguous()
+
+    # ---- IP-Adapter image prompting of the SDR UNet (stable_diffusion_dual_unet.py:518-585, 986-1020) -----------------------------
+    _ip_adapter_supported = True
+
+    def load_ip_adapter(self, path_or_state_dict, subfolder=None, weight_name=None):
+        """diffusers' ``load_ip_adapter`` for LOCAL files: a ``.safetensors`` file whose keys carry the ``image_proj.`` / ``ip_adapter.``
+        prefixes, a ``.bin`` torch pickle of the two dicts (read with ``weights_only=True``), or the already-loaded dict
+        ``{"image_proj": ..., "ip_adapter": ...}``.  ``path_or_state_dict`` may be the file itself or a directory joined with
+        ``subfolder`` and ``weight_name``.  The adapter goes into the SDR UNet (``pipe.gm_unet.load_ip_adapter`` prompts the GM UNet as
+        well); the image encoder is the constructor's ``image_encoder`` and is never loaded from the adapter's folder."""
+        import os
+
+        sd = path_or_state_dict
+        if not isinstance(sd, dict):
+            path = os.fspath(sd)
+            if os.path.isdir(path):
+                if weight_name is None:
+                    raise ValueError("load_ip_adapter: `weight_name` is required when a directory is given")
+                path = os.path.join(path, subfolder or "", weight_name)
+            if not os.path.isfile(path):
+                raise FileNotFoundError(f"load_ip_adapter: {path} is not a local file (nothing is downloaded)")
+            if path.endswith(".safetensors"):
+                from safetensors import safe_open
+
+                sd = {"image_proj": {}, "ip_adapter": {}}
+                with safe_open(path, framework="pt", device="cpu") as f:
+                    for key in f.keys():
+                        if key.startswith("image_proj."):
+                            sd["image_proj"][key[len("image_proj."):]] = f.get_tensor(key)
+                        elif key.startswith("ip_adapter."):
+                            sd["ip_adapter"][key[len("ip_adapter."):]] = f.get_tensor(key)
+            else:
+                sd = torch.load(path, map_location="cpu", weights_only=True)
+        if not isinstance(sd, dict) or sorted(sd.keys()) != ["image_proj", "ip_adapter"]:
+            raise ValueError("Required keys are (`image_proj` and `ip_adapter`) missing from the state dict.")
+        self.unet.load_ip_adapter(sd)
+
+    def unload_ip_adapter(self):
+        self.unet.unload_ip_adapter()
+
+    def set_ip_adapter_scale(self, scale):
+        self.unet.set_ip_adapter_scale(scale)
+
+    def encode_image(self, image, device, num_images_per_prompt, output_hidden_states=None):
+        """stable_diffusion_dual_unet.py:518-540.  ``image_encoder`` / ``feature_extractor`` are whatever the constructor got
+        (``image_encoder(pixels).image_embeds``; transformers' CLIPVisionModelWithProjection works); they run in torch, once per call."""
+        if output_hidden_states:
+            raise NotImplementedError("IP-Adapter Plus (hidden states of the image encoder through a Resampler) is not implemented")
+        if getattr(self, "image_encoder", None) is None:
+            raise ValueError("`ip_adapter_image` needs an `image_encoder` (constructor argument); pass `ip_adapter_image_embeds` instead")
+        params = getattr(self.image_encoder, "parameters", None)
+        first = next(iter(params()), None) if callable(params) else None
+        dtype = first.dtype if first is not None else torch.float32
+        if not isinstance(image, torch.Tensor):
+            if getattr(self, "feature_extractor", None) is None:
+                raise ValueError("`ip_adapter_image` that is not a tensor of pixel values needs a `feature_extractor`")
+            image = self.feature_extractor(image, return_tensors="pt").pixel_values
+        image = image.to(device=device, dtype=dtype)
+        image_embeds = self.image_encoder(image).image_embeds
+        image_embeds = image_embeds.repeat_interleave(num_images_per_prompt, dim=0)
+        uncond_image_embeds = torch.zeros_like(image_embeds)
+        return image_embeds, uncond_image_embeds
+
+    def prepare_ip_adapter_image_embeds(self, ip_adapter_image, ip_adapter_image_embeds, device, num_images_per_prompt,
+                                        do_classifier_free_guidance):
+        """stable_diffusion_dual_unet.py:542-585: a list with one tensor per adapter, [negative; positive] rows under guidance (zeros
+        are the negative image embedding; given embeddings carry their own negative half and are ``chunk(2)``-ed)."""
+        image_embeds = []
+        if do_classifier_free_guidance:
+            negative_image_embeds = []
+        n_adapters = 1 if self.unet.has_ip_adapter else 0
+        if ip_adapter_image_embeds is None:
+            if not isinstance(ip_adapter_image, list):
+                ip_adapter_image = [ip_adapter_image]
+            if len(ip_adapter_image) != n_adapters:
+                raise ValueError(f"`ip_adapter_image` must have same length as the number of IP Adapters. Got {len(ip_adapter_image)} "
+                                 f"images and {n_adapters} IP Adapters.")
+            for single_ip_adapter_image in ip_adapter_image:
+                single_image_embeds, single_negative_image_embeds = self.encode_image(single_ip_adapter_image, device, 1, False)
+                image_embeds.append(single_image_embeds[None, :])
+                if do_classifier_free_guidance:
+                    negative_image_embeds.append(single_negative_image_embeds[None, :])
+        else:
+            for single_image_embeds in ip_adapter_image_embeds:
+                if do_classifier_free_guidance:
+                    single_negative_image_embeds, single_image_embeds = single_image_embeds.chunk(2)
+                    negative_image_embeds.append(single_negative_image_embeds)
+                image_embeds.append(single_image_embeds)
+        ip_adapter_image_embeds = []
+        for i, single_image_embeds in enumerate(image_embeds):
+            single_image_embeds = torch.cat([single_image_embeds] * num_images_per_prompt, dim=0)
+            if do_classifier_free_guidance:
+                single_negative_image_embeds = torch.cat([negative_image_embeds[i]] * num_images_per_prompt, dim=0)
+                single_image_embeds = torch.cat([single_negative_image_embeds, single_image_embeds], dim=0)
+            single_image_embeds = single_image_embeds.to(device=device)
+            ip_adapter_image_embeds.append(single_image_embeds)
+        return ip_adapter_image_embeds
+
+    def _image_prompt_rows(self, ip_adapter_image, ip_adapter_image_embeds, device, rows, do_cfg):
+        """The one adapter's image embeddings [(2 if do_cfg else 1) * rows, n_images, clip_dim], or None without an image prompt.
+        No broadcasting: a row count other than the latents' (doubled under guidance) is an error, as in diffusers."""
+        if ip_adapter_image is None and ip_adapter_image_embeds is None:
+            return None
+        if not self.unet.has_ip_adapter:
+            raise ValueError("an image prompt was given but no IP-Adapter is loaded: call load_ip_adapter() first")
+        embeds = self.prepare_ip_adapter_image_embeds(ip_adapter_image, ip_adapter_image_embeds, device, rows, do_cfg)
+        if len(embeds) != 1:
+            raise NotImplementedError(f"{len(embeds)} image-embedding tensors: several IP-Adapters at once are not implemented")
+        e = embeds[0]
+        if e.dim() == 4:
+            raise NotImplementedError("4-D image embeddings (hidden states for IP-Adapter Plus) are not implemented")
+        want = (2 if do_cfg else 1) * rows
+        if e.dim() != 3 or e.shape[0] != want:
+            raise ValueError(f"the image prompt has {e.shape[0]} rows for {want} UNet rows (batch x num_images_per_prompt"
+                             f"{', doubled under guidance' if do_cfg else ''}); given embeddings are repeated, never broadcast")
+        return e
 
     @staticmethod
     def _control_keep(n, start, end):
@@ -229,6 +354,12 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         if do_cfg:
             prompt_embeds = torch.cat([negative_prompt_embeds, prompt_embeds])
         gm_prompt_embeds = prompt_embeds[n_neg:]  # conditional half (vis.py:274)
+        # dual.py:986-993: the image prompt, [negative; positive] rows like the text.  Only the SDR UNet is image-prompted, unless an
+        # adapter was loaded into the GM UNet itself: it then gets the positive rows, like its prompt embeddings
+        image_rows = self._image_prompt_rows(ip_adapter_image, ip_adapter_image_embeds, device, batch_size * num_images_per_prompt, do_cfg)
+        gm_image_rows = None
+        if image_rows is not None and self.gm_unet.has_ip_adapter:
+            gm_image_rows = image_rows[image_rows.shape[0] // 2:] if do_cfg else image_rows
 
         timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas)
 
@@ -248,6 +379,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         self.gm_scheduler = copy.deepcopy(self.scheduler)  # dual.py:1037, after set_timesteps
 
         sdr_added, gm_added = self._batched_added_cond(added_cond, do_cfg, latents.device)
+        ip_ctx = gm_ip_ctx = None
         fused = self._use_fused(latents, self.unet, self.scheduler) and self._use_fused(latents, self.gm_unet, self.gm_scheduler)
         keep = None  # per step: does the ControlNet run (diffusers' control guidance window); None without a controlnet
         if cn is not None:
@@ -269,6 +401,11 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             self.gm_unet.set_added_cond(gm_added, latents.shape[0])
             self.unet.set_timestep_cond(timestep_cond, (2 if do_cfg else 1) * latents.shape[0])
             self.gm_unet.set_timestep_cond(gm_timestep_cond, latents.shape[0])
+            # the image prompt: projected and turned into every layer's K_ip / V_ip^T once, outside any graph
+            if image_rows is not None:
+                ip_ctx = self.unet.prepare_ip_context(image_rows.to(latents.device))
+            if gm_image_rows is not None:
+                gm_ip_ctx = self.gm_unet.prepare_ip_context(gm_image_rows.to(latents.device))
             # The GM UNet of step i needs only x0_i; the SDR UNet of step i+1 needs only latents_{i+1}: the two are
             # independent, so the GM stream runs on its own HIP stream one step behind the SDR stream and their
             # kernels overlap (the batch-B GM kernels alone cannot fill 256 CUs).
@@ -295,12 +432,12 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                 cn_skip = nb_sdr - cn_rows
             if self._graphs_ok():
                 if cn is None or not all(keep):
-                    g_sdr = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run)
+                    g_sdr = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run, ip=ip_ctx)
                 if cn is not None and any(keep):
                     g_cn = cn.graphed_forward(cn_rows, h, w, cn_ctx, co_run=co_run)
                     control = (g_cn.down, g_cn.mid, cn_scales, cn_skip)
-                    g_sdr_c = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run, control=control)
-                g_gm = self.gm_unet.graphed_forward(latents.shape[0], h, w, gm_ctx, co_run=co_run)
+                    g_sdr_c = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run, control=control, ip=ip_ctx)
+                g_gm = self.gm_unet.graphed_forward(latents.shape[0], h, w, gm_ctx, co_run=co_run, ip=gm_ip_ctx)
             pre = self._predraw_step_noise([self.scheduler, self.gm_scheduler], ts_host, latents.shape, generator, latents.device,
                                            eta=extra_step_kwargs.get("eta", 0.0))
             gm_stream.wait_stream(sdr_stream)
@@ -308,7 +445,12 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                 # allocated on the caller's stream, consumed (and released) by step 0 on the GM stream: without this the
                 # allocator may hand the block to the SDR stream's step 1 while GM step 0 still reads it
                 gm_latents.record_stream(gm_stream)
-        elif getattr(self.scheduler, "sigma_space", False):
+        elif image_rows is not None:
+            # dual.py:1017-1022, 1058: added_cond_kwargs = {"image_embeds": [...]}, diffusers' list with one tensor per adapter
+            sdr_added = {**(sdr_added or {}), "image_embeds": [image_rows.to(latents.device)]}
+            if gm_image_rows is not None:
+                gm_added = {**(gm_added or {}), "image_embeds": [gm_image_rows.to(latents.device)]}
+        if not fused and getattr(self.scheduler, "sigma_space", False):
             raise ValueError(
                 f"{type(self.scheduler).__name__} is a sigma-space scheduler; the dual-UNet pipeline runs it on the fused device path only"
                 " (float32 latents on the GPU with the HIP UNets).  The generic loop restates the reference, which indexes"
@@ -336,11 +478,11 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     elif use_cn:
                         with ops.plan_family(co_run):
                             c_down, c_mid = cn.forward_packed(cx, cn_rows, h, w, cn_ctx)
-                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared,
+                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx,
                                                                       control=(c_down, c_mid, cn_scales, cn_skip))
                     else:
                         with ops.plan_family(co_run):
-                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared)
+                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx)
                     pre_step = latents
                     latents, x0_latent = self.scheduler.fused_step(sdr_noise_pred, ts_host[i], pre_step, do_cfg, self.guidance_scale,
                                                                    self.guidance_rescale if do_cfg else 0.0, want_x0=True,
@@ -357,7 +499,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                             gm_noise_pred = g_gm.replay()
                         else:
                             with ops.plan_family(co_run):
-                                gm_noise_pred = self.gm_unet.forward_packed(gx, gx.shape[0], h, w, gm_ctx)
+                                gm_noise_pred = self.gm_unet.forward_packed(gx, gx.shape[0], h, w, gm_ctx, ip=gm_ip_ctx)
                         gm_latents = self.gm_scheduler.step(gm_noise_pred, ts_host[i], gm_latents,
                                                             **self._fused_step_kwargs(extra_step_kwargs),
                                                             **({"noise": pre[1][i]} if pre else {}), return_dict=False)[0]

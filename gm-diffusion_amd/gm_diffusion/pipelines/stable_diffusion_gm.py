@@ -101,6 +101,7 @@ class _GMPipelineBase(DiffusionPipeline):
     _optional_components = ["safety_checker", "feature_extractor", "image_encoder"]
     _exclude_from_cpu_offload = ["safety_checker"]
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
+    _ip_adapter_supported = False  # image prompts (ip_adapter_image / ip_adapter_image_embeds): the dual-UNet pipeline only
 
     def _init_common(self, vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor,
                      image_encoder, requires_safety_checker, **extra_modules):
@@ -270,7 +271,15 @@ class _GMPipelineBase(DiffusionPipeline):
             raise ValueError("Provide either `ip_adapter_image` or `ip_adapter_image_embeds`. Cannot leave both `ip_adapter_image`"
                              " and `ip_adapter_image_embeds` defined.")
         if ip_adapter_image is not None or ip_adapter_image_embeds is not None:
-            raise NotImplementedError("IP-Adapter conditioning is not part of the GM-Diffusion hot path")
+            if not self._ip_adapter_supported:
+                raise NotImplementedError(f"IP-Adapter conditioning is not implemented for {type(self).__name__}: image prompts run in "
+                                          "StableDiffusionDualUNetPipeline (load_ip_adapter, ip_adapter_image / ip_adapter_image_embeds)")
+            if ip_adapter_image_embeds is not None:  # stable_diffusion_dual_unet.py:688-696
+                if not isinstance(ip_adapter_image_embeds, list):
+                    raise ValueError(f"`ip_adapter_image_embeds` has to be of type `list` but is {type(ip_adapter_image_embeds)}")
+                elif ip_adapter_image_embeds[0].ndim not in [3, 4]:
+                    raise ValueError("`ip_adapter_image_embeds` has to be a list of 3D or 4D tensors but is"
+                                     f" {ip_adapter_image_embeds[0].ndim}D")
 
     def prepare_latents(self, batch_size, num_channels_latents, height, width, dtype, device, generator, latents=None):
         """stable_diffusion_gm.py:696-716"""

@@ -555,6 +555,19 @@ int gmd_attention(const void* Q, const void* K, const void* Vt, void* O, int dty
                   int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldo,
                   int64_t strideQ, int64_t strideK, int64_t strideVt, int64_t strideO,
                   float scale, int causal, gmd_stream_t stream);
+/* Decoupled cross-attention of an IP-Adapter as one launch (added within ABI v14; csrc/attention_ip.hip), GMD_BF16 / GMD_F16:
+ *   O = softmax(scale Q K^T) V  +  ip_scale[ip_scale_index] * softmax(scale Q Kip^T) Vip
+ * Two INDEPENDENT softmaxes (a maximum and a row sum each); Q is read once, O stored once (one rounding), nothing in between reaches
+ * global memory.  Q, K, Vt, O, D as gmd_attention; Kip [B, Nip, *] (ldkip), Vtip [B, H*D, ldvtip] with 1 <= Nip <= 64 (one key tile),
+ * ldvtip >= Nip rounded up to 8.  ip_scale: float32 DEVICE array read by the kernel, so a captured graph serves every scale; the
+ * host rewrites it outside a captured graph.  B == 0 or Nq == 0: GMD_OK, nothing written.  float32 tensors compose gmd_attention
+ * twice and gmd_scaled_add.  reference: IPAdapterAttnProcessor of diffusers, as installed by load_ip_adapter
+ * (stable_diffusion_dual_unet.py:518-585). */
+int gmd_attention_ip(const void* Q, const void* K, const void* Vt, const void* Kip, const void* Vtip, void* O, int dtype,
+                     int B, int H, int D, int Nq, int Nk, int Nip,
+                     int64_t ldq, int64_t ldk, int64_t ldvt, int64_t ldkip, int64_t ldvtip, int64_t ldo,
+                     int64_t strideQ, int64_t strideK, int64_t strideVt, int64_t strideKip, int64_t strideVtip, int64_t strideO,
+                     float softmax_scale, const float* ip_scale, int ip_scale_index, gmd_stream_t stream);
 /* causal != 0 (needs Nq == Nk): query q attends keys 0..q only -- the CLIP text encoder's mask
  * (transformers CLIPTextModel, used through stable_diffusion_gm.py:398-439). */
 
@@ -638,6 +651,10 @@ int gmd_embedding_lookup(const int32_t* ids, const void* table, const void* pos,
  * (stable_diffusion_dual_unet.py:1045-1047 torch.cat([latents] * 2)) applied to an activation where the two conditionings
  * first differ (the CFG shared prefix of UNet2DConditionModel.forward_packed) */
 int gmd_dup_batch(const void* in, void* out, int64_t bytes, gmd_stream_t stream);
+/* out[i] = a[i] + b[i] * scales[index], n elements (a multiple of 8 (16-bit) / 4 (float32)), float32 inside, one rounding on the
+ * store; scales is a float32 DEVICE array.  out may alias a.  The combine of the composed decoupled cross-attention (added within
+ * ABI v14). */
+int gmd_scaled_add(const void* a, const void* b, void* out, int dtype, int64_t n, const float* scales, int index, gmd_stream_t stream);
 /* elementwise cast between F32 and BF16 */
 int gmd_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, gmd_stream_t stream);
 
