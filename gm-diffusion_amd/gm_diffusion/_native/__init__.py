@@ -89,6 +89,7 @@ SIGNATURES = {
     "gmd_silu": [P, I, L, P],
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
     "gmd_scaled_add": [P, P, P, I, L, P, I, P],
+    "gmd_lora_update": [P, P, P, P, I, I, I, I, I, L, L, I, I, I, L, P, I, P],
     "gmd_cast": [P, I, P, I, L, P],
     "gmd_dup_batch": [P, P, L, P],
 }

@@ -1,0 +1,170 @@
+"""
+LoRA adapters for the UNet: reading the checkpoint conventions in the wild into ONE canonical form.  Host-only (torch on the CPU,
+no HIP): the device side is ``UNet2DConditionModel.load_lora`` and ``hip_ops.lora_update``.
+
+diffusers and peft are not dependencies of this package, so the three key conventions below are this repository's restatement of
+what their loaders accept (diffusers ``LoraLoaderMixin.lora_state_dict`` and its kohya conversion), not an import:
+
+  PEFT / current diffusers   [unet.]<module>.lora_A.weight  [r, in]     [unet.]<module>.lora_B.weight  [out, r]    [<module>.alpha]
+  older diffusers            [unet.]<module>.lora.down.weight           [unet.]<module>.lora.up.weight
+                             [unet.]<block>.attn1.processor.to_q_lora.down.weight / .up.weight   (to_out_lora -> to_out.0)
+  kohya                      lora_unet_<module with "." -> "_">.lora_down.weight / .lora_up.weight / .alpha
+
+A module's update is  W + scale * (alpha / r) * up @ down  (factor 1 without an alpha).  kohya names are resolved against the model's
+OWN module names with the dots replaced -- never by splitting on underscores, which ``to_out_0`` and ``transformer_blocks_0`` defeat.
+
+What the UNet applies (``SUPPORTED_SUFFIXES``): the eight attention projections of every BasicTransformerBlock -- the target set of
+diffusers' train_text_to_image_lora.py.  Everything else is refused BY NAME (``NotImplementedError``) unless ``ignore_unsupported``,
+which skips it with one warning listing the modules: a silently thinner adapter is never the default.
+"""
+import re
+import warnings
+
+import torch
+
+from ..hip_ops import LORA_MAX_RANK as MAX_RANK  # the kernel's limit; importing hip_ops needs no GPU
+
+SUPPORTED_SUFFIXES = tuple(f"{a}.{p}" for a in ("attn1", "attn2") for p in ("to_q", "to_k", "to_v", "to_out.0"))
+
+# key fragments of adapter families that are no plain linear LoRA at all
+_FOREIGN = ("hada_", "lokr_", "dora_scale", "lora_mid", "lora_magnitude_vector")
+_TEXT_PREFIXES = ("text_encoder.", "text_encoder_2.", "lora_te_", "lora_te1_", "lora_te2_")
+
+_DOWN, _UP, _ALPHA = "down", "up", "alpha"
+# (suffix of the key, which part it is); longest first
+_PARTS = ((".lora_A.weight", _DOWN), (".lora_B.weight", _UP), (".lora.down.weight", _DOWN), (".lora.up.weight", _UP),
+          (".lora_down.weight", _DOWN), (".lora_up.weight", _UP), (".alpha", _ALPHA))
+_PROCESSOR = re.compile(r"^(.*)\.processor\.(to_q|to_k|to_v|to_out)_lora\.(down|up)\.weight$")
+
+
+def supported(module):
+    """Is ``module`` one of the projections the UNet applies an adapter to?"""
+    return ".transformer_blocks." in module and module.endswith(SUPPORTED_SUFFIXES)
+
+
+def _why_unsupported(module):
+    if ".ff.net." in module:
+        return "feed-forward target (the GEGLU kernel is fused)"
+    if module.endswith(("proj_in", "proj_out")):
+        return "proj_in / proj_out target"
+    if "resnets." in module or module.endswith(("time_emb_proj", "conv1", "conv2", "conv_shortcut", "conv", "conv_in", "conv_out")):
+        return "resnet / convolution target"
+    return "not an attention projection of a transformer block"
+
+
+def _split_key(key):
+    """key -> (module name as written, part) or None when the key is no LoRA tensor."""
+    m = _PROCESSOR.match(key)
+    if m:
+        proj = "to_out.0" if m.group(2) == "to_out" else m.group(2)
+        return f"{m.group(1)}.{proj}", m.group(3)
+    for suf, part in _PARTS:
+        if key.endswith(suf):
+            return key[: -len(suf)], part
+    return None
+
+
+def parse_lora_state_dict(sd, module_names, ignore_unsupported=False):
+    """``sd``: a LoRA checkpoint in any of the three conventions (module docstring); ``module_names``: the model's own module names
+    (``down_blocks.0.attentions.0.transformer_blocks.0.attn1.to_q``, ...).  Returns ``{module: (A [r, K], B [N, r], alpha or None)}``
+    with float32 CPU factors, for the supported modules.  Unsupported modules, foreign adapter families, text-encoder keys and ranks
+    above 128 raise ``NotImplementedError`` naming the module; with ``ignore_unsupported`` they are skipped and ONE warning lists them."""
+    module_names = list(module_names)
+    by_flat = {}
+    for n in module_names:
+        by_flat.setdefault(n.replace(".", "_"), n)
+    known = set(module_names)
+    parts, refused = {}, {}
+
+    def refuse(name, why):
+        refused.setdefault(name, why)
+
+    for key, val in sd.items():
+        if key.startswith(_TEXT_PREFIXES):
+            refuse(key.split(".lora")[0], "text-encoder LoRA (the text tower is not adapted)")
+            continue
+        if any(f in key for f in _FOREIGN):
+            refuse(key.rsplit(".", 1)[0] if "." in key else key, "LoHa / LoKr / DoRA / conv-LoRA key (only plain linear LoRA factors are applied)")
+            continue
+        sp = _split_key(key)
+        if sp is None:
+            refuse(key, "not a LoRA tensor (no lora_A / lora_B / lora.down / lora.up / lora_down / lora_up / alpha suffix; stray metadata "
+                        "counts as an unsupported entry, so that nothing of a checkpoint is dropped silently)")
+            continue
+        name, part = sp
+        if name.startswith("lora_unet_"):  # kohya: through the module table
+            flat = name[len("lora_unet_"):]
+            if flat not in by_flat:
+                refuse(name, "no module of this UNet has that flattened name")
+                continue
+            name = by_flat[flat]
+        else:
+            if name.startswith("unet."):
+                name = name[len("unet."):]
+            if name not in known:
+                refuse(name, "no module of this UNet has that name")
+                continue
+        parts.setdefault(name, {})[part] = val
+
+    out = {}
+    for name, p in parts.items():
+        if not supported(name):
+            refuse(name, _why_unsupported(name))
+            continue
+        if _DOWN not in p or _UP not in p:
+            raise KeyError(f"LoRA: module {name} has {sorted(p)} -- both the down (lora_A) and the up (lora_B) factor are needed")
+        a, b = p[_DOWN], p[_UP]
+        if a.dim() != 2 or b.dim() != 2:
+            refuse(name, f"factors of shape {tuple(a.shape)} / {tuple(b.shape)}: convolution LoRA")
+            continue
+        if b.shape[1] != a.shape[0]:
+            raise ValueError(f"LoRA: module {name}: down {tuple(a.shape)} and up {tuple(b.shape)} disagree on the rank")
+        r = a.shape[0]
+        if not 1 <= r <= MAX_RANK:
+            refuse(name, f"rank {r} outside [1, {MAX_RANK}]")
+            continue
+        alpha = p.get(_ALPHA)
+        alpha = None if alpha is None else float(alpha)
+        out[name] = (a.detach().to("cpu", torch.float32).contiguous(), b.detach().to("cpu", torch.float32).contiguous(), alpha)
+
+    if refused:
+        listing = "; ".join(f"{n}: {w}" for n, w in sorted(refused.items()))
+        if not ignore_unsupported:
+            raise NotImplementedError(f"LoRA: {len(refused)} target(s) are not implemented -- {listing}.  Pass ignore_unsupported=True to "
+                                      "apply the adapter without them.")
+        warnings.warn(f"LoRA: skipped {len(refused)} unsupported target(s) -- {listing}", stacklevel=2)
+    return out
+
+
+def factor(rank, alpha):
+    """The adapter's own factor alpha / r (1 without an alpha)."""
+    return 1.0 if alpha is None else float(alpha) / rank
+
+
+def load_lora_file(path_or_state_dict, weight_name=None, subfolder=None):
+    """A LoRA checkpoint from a dict, a file or a directory (+ ``subfolder`` / ``weight_name``): local ``.safetensors``, or ``.bin`` /
+    ``.pt`` with ``weights_only=True``.  Nothing is ever downloaded."""
+    import os
+
+    if isinstance(path_or_state_dict, dict):
+        return path_or_state_dict
+    path = os.fspath(path_or_state_dict)
+    if subfolder:
+        path = os.path.join(path, subfolder)
+    if os.path.isdir(path):
+        names = [weight_name] if weight_name else ["pytorch_lora_weights.safetensors", "pytorch_lora_weights.bin"]
+        for n in names:
+            if os.path.isfile(os.path.join(path, n)):
+                path = os.path.join(path, n)
+                break
+        else:
+            raise FileNotFoundError(f"load_lora_weights: none of {names} in {path} (local files only: nothing is downloaded)")
+    elif weight_name and not os.path.isfile(path):
+        path = os.path.join(path, weight_name)
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"load_lora_weights: {path} does not exist (local files only: nothing is downloaded)")
+    if path.endswith(".safetensors"):
+        from safetensors.torch import load_file
+
+        return load_file(path, device="cpu")
+    return torch.load(path, map_location="cpu", weights_only=True)

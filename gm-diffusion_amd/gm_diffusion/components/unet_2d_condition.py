@@ -233,6 +233,32 @@ def composed_attention(q, q_col, ldq, k, k_col, ldk, vt, B, H, d, nq, nk, scale,
     return out
 
 
+def _lora_layer(model, t):
+    """The LoRA factors of transformer block ``t`` of ``model`` ({projection: (a, b, index)}), or None: no adapter loaded, the block
+    not targeted, or a model that takes none (a ControlNet shares the UNet's block code and is not adapted)."""
+    if getattr(model, "_lora_raw", None) is None:
+        return None
+    lw = model._lora_w
+    if lw is None or model._lora_w_of is not model._w:
+        raise HipExtensionError("the LoRA adapter must be prepared (update_context / a forward) before it is read")
+    return lw["layers"].get(t["key"])
+
+
+def _lora_key(model):
+    return None if getattr(model, "_lora_raw", None) is None else (model._lora_id, model._lora_version)
+
+
+def _lora_apply(model, lr, proj, x, y, col=0, tokens=None, x_split=False):
+    """One ``hip_ops.lora_update`` behind an adapted projection (nothing when the adapter does not target ``proj`` of this block)."""
+    ent = lr.get(proj)
+    if ent is not None:
+        ops.lora_update(x, ent[0], ent[1], y, model._lora_w["scales"], ent[2], transposed=tokens is not None, tokens=tokens, col=col,
+                        x_split=x_split)
+
+
+_LORA_IDS = [0]
+
+
 class _GraphedForward:
     """A captured UNet forward: static input ``x``, static output ``out``, ``replay()`` on the current stream."""
 
@@ -291,6 +317,12 @@ class UNet2DConditionModel(_HipModule):
         self._ip_kv = {}          # ... persistent K_ip / V_ip^T per (layer, rows, Nip, dtype), rewritten in place by prepare_ip_context
         self._ip_scale = 1.0      # ... set_ip_adapter_scale
         self._ip_last = None      # ... (key of the embeddings, their context, the embeddings) of the latest prepare_ip_context
+        self._lora_raw = None     # LoRA: {module: (A [r, K], B [N, r], alpha or None)} CPU float32 (load_lora), None when no adapter is loaded
+        self._lora_w = None       # ... the factors in kernel layouts + the device table of scales, built on first use (_ensure_lora)
+        self._lora_w_of = None
+        self._lora_scale = 1.0    # ... set_lora_scale
+        self._lora_id = 0         # ... identity of the loaded adapter (graph key, cross-attention K / V cache key)
+        self._lora_version = 0    # ... bumped by load_lora / unload_lora / set_lora_scale: cached cross-attention K / V hold the scale
 
     # ------------------------------------------------------------------------------------------
     # structure
@@ -610,17 +642,28 @@ class UNet2DConditionModel(_HipModule):
         heads = t["heads"]
         d = C // heads
         scale = d ** -0.5
+        lr = _lora_layer(self, t)  # None: the launches of a UNet without a LoRA adapter
+
+        def adapted(qk2d, vt):
+            # q | k: column ranges [0, C) / [C, 2C) of the stacked buffer; v: transposed, on whichever V^T this route produced
+            if lr is not None:
+                _lora_apply(self, lr, "attn1.to_q", n1, qk2d)
+                _lora_apply(self, lr, "attn1.to_k", n1, qk2d, col=C)
+                _lora_apply(self, lr, "attn1.to_v", n1, vt, tokens=N)
+            return qk2d.view(B, N, 2 * C), vt
+
         if "qkv1" in t and (ops.is_half(self._dtype) or ops.split_attention_ok(self._dtype, d)):
             r = ops.gemm_qkv_vt(n1, t["qkv1"], 2 * C, N)
             if r is not None:
-                qk = r[0].view(B, N, 2 * C)
-                return ops.attention(qk, qk, r[1], heads, N, scale, k_col=C, split_out=self._sa(t["o1"][0]))
-        qk = ops.gemm_nt(n1, t["qk1"]).view(B, N, 2 * C)
+                qk, vt = adapted(r[0], r[1])
+                return ops.attention(qk, qk, vt, heads, N, scale, k_col=C, split_out=self._sa(t["o1"][0]))
+        qk = ops.gemm_nt(n1, t["qk1"])
         if ops.is_half(self._dtype) or ops.split_attention_ok(self._dtype, d):
             nv = n1.view(B, N, C)
             if ops.is_asplit(n1):  # a pre-split activation as the W operand of V^T = Wv n1^T: exactly the pre-split weight layout
                 nv._split, nv._alpha = True, 1.0
             vt = ops.gemm_nt(t["v1"], nv, ldc=_pad_to(N, 8 if ops.is_half(self._dtype) else 4))  # V^T [B, C, N]
+            qk, vt = adapted(qk, vt)
             return ops.attention(qk, qk, vt, heads, N, scale, k_col=C, split_out=self._sa(t["o1"][0]))
         npad = _pad_to(N, 4)
         if npad != N:
@@ -628,13 +671,16 @@ class UNet2DConditionModel(_HipModule):
             ops.gemm_nt(t["v1"], n1.view(B, N, C), out=vt, ldc=npad)
         else:
             vt = ops.gemm_nt(t["v1"], n1.view(B, N, C), ldc=npad)
+        qk, vt = adapted(qk, vt)
         return composed_attention(qk, 0, 2 * C, qk, C, 2 * C, vt, B, heads, d, N, N, scale, self._dtype)
 
     def _cross_kv(self, t, ehs):
         """K and V^T of the text tokens: constant over the whole denoising loop, so computed once per embedding tensor.
         The buffers are persistent per (layer, shape) and rewritten in place for new embeddings, so a captured HIP
         graph of the forward keeps reading valid addresses."""
-        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
+        lr = _lora_layer(self, t)
+        # with an adapter the cached K / V^T hold its update AT ITS SCALE: the key carries the adapter's identity and version
+        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape), _lora_key(self))
         B, L, E = ehs.shape
         # one persistent buffer pair per (layer, batch, tokens): a graph captured for one batch size must keep finding ITS
         # buffers after the model has served another batch size in between
@@ -652,6 +698,9 @@ class UNet2DConditionModel(_HipModule):
             self._kv_cache[slot] = ent
         ops.gemm_nt(ehs.view(B * L, E), t["k2"], out=ent["kc"].view(B * L, C))
         ops.gemm_nt(t["v2"], ehs, out=ent["vt"], ldc=lpad)
+        if lr is not None:  # a text-side LoRA: once per call on the text tokens, nothing per step
+            _lora_apply(self, lr, "attn2.to_k", ehs.view(B * L, E), ent["kc"].view(B * L, C))
+            _lora_apply(self, lr, "attn2.to_v", ehs.view(B * L, E), ent["vt"], tokens=L)
         ent["key"] = key
         ent["ehs"] = ehs  # holding `ehs` keeps its address from being recycled while the key is valid
         return ent["kc"], ent["vt"]
@@ -661,6 +710,8 @@ class UNet2DConditionModel(_HipModule):
         """Prepare the cross-attention K / V^T of every transformer block for these text hidden states (eager,
         in place).  Called once per pipeline call; required before replaying a captured forward."""
         self._ensure()
+        if getattr(self, "_lora_raw", None) is not None:
+            self._ensure_lora()
         for t in self._transformers:
             self._cross_kv(t, ehs)
 
@@ -872,6 +923,95 @@ class UNet2DConditionModel(_HipModule):
             raise HipExtensionError("IP-Adapter K/V must be prepared (prepare_ip_context) before the forward / graph capture")
         return ent["kc"], ent["vt"], self._ip_w["layers"][t["key"]]["index"]
 
+    # ------------------------------------------------------------------------------------------
+    # LoRA: one adapter, kept in factors and applied at run time (hip_ops.lora_update); components/lora.py reads the checkpoints
+    # ------------------------------------------------------------------------------------------
+    def lora_module_names(self):
+        """The model's own module names, the table kohya's flattened names are resolved against."""
+        return [k[: -len(".weight")] for k in self.expected_keys() if k.endswith(".weight")]
+
+    def load_lora(self, state_dict, ignore_unsupported=False):
+        """Load ONE LoRA adapter (PEFT / diffusers / kohya keys: components/lora.py) for the attention projections of the transformer
+        blocks.  Host work only: the factors go to the device, in the model's dtype and beside the prepared weights, at first use.  No
+        weight buffer changes: every targeted projection is followed by one ``hip_ops.lora_update``."""
+        from . import lora as _lora
+
+        if self._lora_raw is not None:
+            raise NotImplementedError("load_lora: an adapter is already loaded and several adapters at once are not implemented "
+                                      "(unload_lora() first)")
+        parsed = _lora.parse_lora_state_dict(state_dict, self.lora_module_names(), ignore_unsupported=ignore_unsupported)
+        if not parsed:
+            raise ValueError("load_lora: the state dict holds no LoRA factors for this UNet's attention projections")
+        shapes = self.expected_keys()
+        for name, (a, b, _) in parsed.items():
+            n, k = shapes[name + ".weight"][:2]
+            if a.shape[1] != k or b.shape[0] != n:
+                raise ValueError(f"load_lora: {name}: factors {tuple(b.shape)} x {tuple(a.shape)} do not fit the [{n}, {k}] projection")
+        _LORA_IDS[0] += 1
+        self._lora_raw, self._lora_id, self._lora_scale = parsed, _LORA_IDS[0], 1.0
+        self._drop_lora_device_state()
+        return self
+
+    def unload_lora(self):
+        """Back to the UNet without an adapter: the launches, and so the outputs, of a model that never had one."""
+        self._lora_raw = None
+        self._lora_scale = 1.0
+        self._drop_lora_device_state()
+        return self
+
+    def _drop_lora_device_state(self):
+        self._lora_w = self._lora_w_of = None
+        self._lora_version += 1  # cached cross-attention K / V^T were written with (or without) the dropped adapter
+        self._graphs = {k: g for k, g in self._graphs.items() if not any(isinstance(e, tuple) and e[:1] == ("lora",) for e in k)}
+
+    @property
+    def has_lora(self):
+        return self._lora_raw is not None
+
+    def set_lora_scale(self, scale):
+        """The adapter's scale (diffusers' ``cross_attention_kwargs={"scale": s}``; default 1.0): ``scales[i] = s * alpha_i / r_i`` is
+        rewritten in the float32 device table the kernels read -- outside any captured graph, so a captured forward serves every scale.
+        The cross-attention K / V^T are cached per prompt WITH the update, so they are recomputed at the next ``update_context``."""
+        if self._lora_raw is None:
+            raise ValueError("set_lora_scale: no LoRA adapter is loaded")
+        if self._capturing:
+            raise HipExtensionError("the LoRA scale must be set outside graph capture")
+        scale = float(scale)
+        if scale == self._lora_scale:
+            return
+        self._lora_scale = scale
+        self._lora_version += 1
+        if self._lora_w is not None and self._lora_w_of is self._w:
+            self._lora_w["scales"].copy_(self._lora_w["factors"] * scale)
+
+    def _ensure_lora(self):
+        """The adapter's factors in kernel layouts, next to (and for) the prepared UNet weights: the rank zero-padded to the multiple
+        the contractions of this dtype mode need, ``a`` a W operand (pre-split where the weights are), ``b`` a W operand for the plain
+        outputs and an A operand for the V^T outputs (as the model's own to_v weights)."""
+        self._ensure()
+        if self._lora_w is not None and self._lora_w_of is self._w:
+            return self._lora_w
+        if self._capturing:
+            raise HipExtensionError("the LoRA adapter must be prepared (update_context) before graph capture")
+        from . import lora as _lora
+
+        mult = ops.lora_rank_multiple(self._dtype, split=self._split_mode())
+        layers, factors = {}, []
+        for i, name in enumerate(sorted(self._lora_raw)):
+            a, b, alpha = self._lora_raw[name]
+            r = a.shape[0]
+            rp = _pad_to(r, mult)
+            ap, bp = torch.zeros(rp, a.shape[1]), torch.zeros(b.shape[0], rp)
+            ap[:r], bp[:, :r] = a, b
+            blk, proj = name.rsplit(".attn", 1)
+            proj = "attn" + proj
+            layers.setdefault(blk, {})[proj] = (self._wt(ap), self._wa(bp) if proj.endswith("to_v") else self._wt(bp), i)
+            factors.append(_lora.factor(r, alpha))
+        factors = torch.tensor(factors, dtype=torch.float32)
+        w = dict(layers=layers, factors=factors, scales=(factors * self._lora_scale).to(self._device))
+        self._lora_w, self._lora_w_of = w, self._w
+        return w
+
     @staticmethod
     def _dup_batch(t):
         """[B, ...] -> [2B, ...]: both halves equal to ``t`` (gmd_dup_batch: one read, two writes)."""
@@ -903,11 +1043,17 @@ class UNet2DConditionModel(_HipModule):
         # self-attention
         # (the V^T product takes n1 as its W operand: pre-split only where the matrix-core attention path is taken)
         n1 = ops.layernorm(h, *t["norm1"], split_out=self._sa(t["qk1"]) and ops.split_attention_ok(self._dtype, d))
+        lr = _lora_layer(self, t)  # None: the launches of a UNet without a LoRA adapter
         o = self._self_attention(t, n1, B, N, C)
         h = ops.gemm_nt(o.view(B * N, C), t["o1"][0], bias=t["o1"][1], residual=h, a_split=ops.is_asplit(o))
+        if lr is not None:  # after the bias + residual epilogue: the update commutes with both
+            _lora_apply(self, lr, "attn1.to_out.0", o.view(B * N, C), h, x_split=ops.is_asplit(o))
         # cross-attention over the text tokens
         n2 = ops.layernorm(h, *t["norm2"], split_out=self._sa(t["q2"]))
-        q = ops.gemm_nt(n2, t["q2"]).view(B, N, C)
+        q = ops.gemm_nt(n2, t["q2"])
+        if lr is not None:  # (under cfg_dup: on the B unique rows, before the duplication)
+            _lora_apply(self, lr, "attn2.to_q", n2, q)
+        q = q.view(B, N, C)
         if cfg_dup:  # first use of the text conditioning: from here on the two halves differ
             q, h, x = self._dup_batch(q), self._dup_batch(h.view(B, N, C)).view(2 * B * N, C), self._dup_batch(x)
             B *= 2
@@ -927,6 +1073,8 @@ class UNet2DConditionModel(_HipModule):
         else:
             o = composed_attention(q, 0, C, kc, 0, C, vtc, B, heads, d, N, L, d ** -0.5, self._dtype)
         h = ops.gemm_nt(o.view(B * N, C), t["o2"][0], bias=t["o2"][1], residual=h, a_split=ops.is_asplit(o))
+        if lr is not None:
+            _lora_apply(self, lr, "attn2.to_out.0", o.view(B * N, C), h, x_split=ops.is_asplit(o))
         # GEGLU feed-forward
         n3 = ops.layernorm(h, *t["norm3"], split_out=self._sa(t["ff1"][0]))
         if t["ff1_fused"] and ops.ff_fused_ok(n3, C):  # the whole feed-forward in one launch: [tokens, 4C] never reaches HBM
@@ -1152,6 +1300,8 @@ class UNet2DConditionModel(_HipModule):
             raise HipExtensionError("cfg_shared needs an even batch and a transformer in the first down block")
         if ip is not None:
             self._check_ip(ip, B)
+        if self._lora_raw is not None:
+            self._ensure_lora()
         temb = self._time_embedding(w, B)
         Bc = B // 2 if cfg_shared else B  # rows currently carried (the unique half until the first cross-attention)
         x, skips, H, W = self._down_mid(w, x, B, Bc, H, W, temb, ehs, mark, ip=ip)
@@ -1215,6 +1365,9 @@ class UNet2DConditionModel(_HipModule):
         if ip is not None:
             self._check_ip(ip, B)
             key += (("ip", ip.rows, ip.nip),)
+        if self._lora_raw is not None:  # the graph holds the adapter's launches and reads its factors and its table of scales
+            self._ensure_lora()
+            key += (("lora", self._lora_id),)
         g = self._graphs.get(key)
         if g is not None:
             return g

@@ -898,6 +898,77 @@ def attention_ip(q, k, vt, kip, vtip, heads, nk, nip, scale, ip_scales, ip_index
     return o
 
 
+# A LoRA adapter applied at run time: y += scales[index] * (x a^T) b^T.  The 16-bit types take ONE launch (gmd_lora_update);
+# GMD_LORA_FUSED=0 (read once) sends them down the composed route instead -- two gemm_nt launches and scaled_add, what float32 always
+# runs: the A/B switch.
+USE_LORA_FUSED = os.environ.get("GMD_LORA_FUSED", "1") != "0"
+LORA_MAX_RANK = 128  # the kernel's limit (components/lora.py refuses larger adapters at load with this very number)
+
+
+def lora_rank_multiple(dtype, split=None):
+    """Multiple the host zero-pads an adapter's rank to: 32 for the fused 16-bit launch, the K multiple of the float32 contraction
+    mode otherwise (``split``: a module's own recorded mode; default: the calling thread's)."""
+    split = (f32_mode() == "split") if split is None else bool(split)
+    return 32 if (is_half(dtype) or split) else 16
+
+
+def lora_update(x, a, b, y, scales, index, transposed=False, tokens=None, fused=None, col=0, x_split=False):
+    """``y += scales[index] * (x @ a.T) @ b.T`` in place; returns ``y``.  x: [M, K]; a: [Rp, K] and b: [N, Rp], the adapter's factors
+    with the rank zero-padded to ``lora_rank_multiple`` (float32: prepared like the model's weights, a pre-split ``a`` for a pre-split
+    ``x``).  Plain mode: y is a contiguous [M, ldy] buffer and columns [col, col + N) of it are updated (the q and k ranges of a stacked
+    q | k buffer).  ``transposed``: y is a contiguous V^T [batch, N, ldy] with M = batch * ``tokens`` and row b * tokens + tok of the
+    update lands at y[b, n, tok]; the pad columns [tokens, ldy) are not touched.  ``scales``: float32 device tensor read by the kernels, so
+    a captured graph serves every scale.  ``x_split``: x is a VIEW of a pre-split activation (views do not carry the mark).  16-bit types:
+    one launch (gmd_lora_update) unless ``fused`` is False (default: USE_LORA_FUSED); float32: two gemm_nt launches and scaled_add."""
+    _dev(x, a, b, y, scales)
+    index = _ip_scale_arg(scales, index, "lora_update")
+    if not (x.dtype == a.dtype == b.dtype == y.dtype):
+        raise HipExtensionError(f"lora_update: dtype mismatch {x.dtype} / {a.dtype} / {b.dtype} / {y.dtype}")
+    if x.dim() != 2 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != x.shape[1] or b.shape[1] != a.shape[0]:
+        raise HipExtensionError(f"lora_update: operand shapes inconsistent: x {tuple(x.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)}")
+    if is_asplit(y):
+        raise HipExtensionError("lora_update: y is a pre-split activation (only contractions read that layout)")
+    M, K = x.shape
+    N, Rp = b.shape
+    if transposed:
+        if y.dim() != 3 or tokens is None or tokens <= 0 or y.shape[0] * tokens != M or y.shape[1] != N or y.shape[2] < tokens or col:
+            raise HipExtensionError(f"lora_update: transposed y {tuple(y.shape)} does not hold [M / tokens, N, >= tokens] for M={M}, N={N}, "
+                                    f"tokens={tokens}")
+        batch, ldy = y.shape[0], y.shape[2]
+    else:
+        if y.dim() != 2 or y.shape[0] != M or col < 0 or col + N > y.shape[1]:
+            raise HipExtensionError(f"lora_update: y {tuple(y.shape)} does not hold columns [{col}, {col + N}) of {M} rows")
+        batch, tokens, ldy = 1, M, y.shape[1]
+    fused = USE_LORA_FUSED if fused is None else bool(fused)
+    if is_half(x.dtype) and K % 64:
+        raise HipExtensionError(f"lora_update: K={K} must be a multiple of 64 in the 16-bit types (the fused launch and gemm_nt alike)")
+    if is_half(x.dtype) and not transposed and N % 8:
+        fused = False  # the fused launch moves Y in 16-byte pieces of a row: a ragged N takes the composed route
+    if is_half(x.dtype) and fused:
+        if Rp > LORA_MAX_RANK:
+            raise HipExtensionError(f"lora_update: padded rank {Rp} above {LORA_MAX_RANK}")
+        tm, t0 = _timed("lora_update")
+        check(lib().gmd_lora_update(_ptr(x), _ptr(a), _ptr(b), y.data_ptr() + col * y.element_size(), dtype_code(x.dtype), M, K, Rp, N, K, ldy,
+                                    int(bool(transposed)), batch, tokens, N * ldy, _ptr(scales), index, _stream()), "gmd_lora_update")
+        if tm:
+            tm.end("lora_update", 2.0 * M * Rp * (K + N), (M * K + 2 * M * N + Rp * (K + N)) * x.element_size(), t0)
+        return y
+    # composed: T = x a^T, U = T b^T in y's layout (zero where y is not updated: s * 0 leaves those elements), y += s U
+    if is_half(x.dtype) and Rp % 64:  # the 16-bit gemm_nt contracts over multiples of 64: more zero rank columns (A/B route only)
+        a = torch.nn.functional.pad(a, (0, 0, 0, 64 - Rp % 64))
+        b = torch.nn.functional.pad(b, (0, 64 - Rp % 64))
+        Rp = b.shape[1]
+    t = gemm_nt(x, a, a_split=bool(x_split) or is_asplit(x))
+    # zero where y is not updated; where the second product writes every element of u nothing needs clearing
+    covers = (ldy == tokens) if transposed else (col == 0 and ldy == N)
+    u = torch.empty_like(y) if covers else torch.zeros_like(y)
+    if transposed:
+        gemm_nt(b, t.view(batch, tokens, Rp), out=u, ldc=ldy)  # U[b] = b T[b]^T: [N, tokens], the V^T layout
+    else:
+        gemm_nt(t, b, out=u.view(-1)[col:], ldc=ldy)
+    return scaled_add(y, u, scales, index, out=y)
+
+
 def softmax_rows(s, cols, scale, out_dtype, ldp=None, causal_nq=0):
     _dev(s)
     _f32(s, "softmax_rows input")

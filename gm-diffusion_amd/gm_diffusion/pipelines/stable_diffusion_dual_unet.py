@@ -79,7 +79,7 @@ from typing import Any, Callable, Dict, List, Optional, Union
 import torch
 
 from .. import hip_ops as ops
-from .stable_diffusion_gm import _GMPipelineBase, rescale_noise_cfg, retrieve_timesteps
+from .stable_diffusion_gm import _GMPipelineBase, _per_call_lora_scale, rescale_noise_cfg, retrieve_timesteps
 
 __all__ = ["StableDiffusionDualUNetPipeline", "rescale_noise_cfg", "retrieve_timesteps"]
 
@@ -278,6 +278,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
     def _gm_stream(self, device):
         return ops.side_stream(device)  # one per device for the whole process, not per pipeline object (see there)
 
+    @_per_call_lora_scale
     @torch.no_grad()
     def __call__(
         self,
@@ -345,6 +346,7 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
             control_image = self._prepare_control_image(kwargs.pop("control_image", None), height, width,
                                                         batch_size * num_images_per_prompt, "cpu")
         lora_scale = self.cross_attention_kwargs.get("scale", None) if self.cross_attention_kwargs is not None else None
+        self._apply_lora_scale(lora_scale)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, device, num_images_per_prompt, self.do_classifier_free_guidance, negative_prompt,
             prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, lora_scale=lora_scale,

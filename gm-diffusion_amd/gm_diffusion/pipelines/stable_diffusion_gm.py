@@ -37,12 +37,14 @@ the reference; what runs underneath is the MI355X path:
 Behaviour notes kept from the reference: the latent channel count is forced to 4 and the latent
 size is taken from ``sdr_latent`` (:1003-1015, ``height``/``width`` are ignored); unknown
 ``**kwargs`` are ignored (callers pass ``noise_level=``); per-call state lives on ``self``
-(not re-entrant).  LoRA / textual-inversion / IP-adapter mixins of the diffusers base are not
-part of this path: ``cross_attention_kwargs['scale']`` is accepted and ignored, ``ip_adapter_*``
-raise ``NotImplementedError``.
+(not re-entrant).  The textual-inversion / IP-adapter mixins of the diffusers base are not part
+of this path (``ip_adapter_*`` raise ``NotImplementedError``).  LoRA: ``load_lora_weights`` loads ONE
+adapter from a local file, kept in factors and applied at run time (hip_ops.lora_update);
+``cross_attention_kwargs['scale']`` is its weight for the call (nothing without an adapter).
 """
 from __future__ import annotations
 
+import functools
 import inspect
 import logging
 import warnings
@@ -65,6 +67,18 @@ def rescale_noise_cfg(noise_cfg, noise_pred_text, guidance_rescale=0.0):
     noise_pred_rescaled = noise_cfg * (std_text / std_cfg)
     noise_cfg = guidance_rescale * noise_pred_rescaled + (1 - guidance_rescale) * noise_cfg
     return noise_cfg
+
+
+def _per_call_lora_scale(call):
+    """A pipeline ``__call__`` whose ``cross_attention_kwargs["scale"]`` holds for that call only (also when it raises)."""
+    @functools.wraps(call)
+    def wrapped(self, *args, **kwargs):
+        try:
+            return call(self, *args, **kwargs)
+        finally:
+            self._restore_lora_scale()
+
+    return wrapped
 
 
 def retrieve_timesteps(scheduler, num_inference_steps: Optional[int] = None, device=None,
@@ -102,6 +116,57 @@ class _GMPipelineBase(DiffusionPipeline):
     _exclude_from_cpu_offload = ["safety_checker"]
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     _ip_adapter_supported = False  # image prompts (ip_adapter_image / ip_adapter_image_embeds): the dual-UNet pipeline only
+
+    # ---- LoRA (diffusers' StableDiffusionLoraLoaderMixin, for LOCAL files; one adapter, kept in factors) ---------------------------
+    def load_lora_weights(self, path_or_state_dict, weight_name=None, subfolder=None, ignore_unsupported=False, adapter_name=None, **kwargs):
+        """diffusers' ``load_lora_weights`` for LOCAL files: a ``.safetensors`` file, a ``.bin`` / ``.pt`` torch pickle (read with
+        ``weights_only=True``), a directory joined with ``subfolder`` and ``weight_name``, or the already-loaded state dict, in the
+        PEFT, older diffusers or kohya key convention (components/lora.py).  Nothing is ever downloaded.  The adapter goes into
+        ``self.unet`` (the dual pipeline: the SDR UNet; ``pipe.gm_unet.load_lora(...)`` adapts the GM UNet) and is applied at run
+        time by one fused launch per targeted projection; targets that are not built raise unless ``ignore_unsupported``."""
+        from ..components import lora as _lora
+
+        if adapter_name is not None:
+            raise NotImplementedError("load_lora_weights(adapter_name=...): one adapter at a time is implemented, kept in factors and "
+                                      "applied at run time; there are no named adapters to switch between")
+        if kwargs:
+            raise NotImplementedError(f"load_lora_weights: unsupported arguments {sorted(kwargs)} (local files only)")
+        self.unet.load_lora(_lora.load_lora_file(path_or_state_dict, weight_name=weight_name, subfolder=subfolder),
+                            ignore_unsupported=ignore_unsupported)
+
+    def unload_lora_weights(self):
+        self.unet.unload_lora()
+
+    def fuse_lora(self, *args, **kwargs):
+        raise NotImplementedError("fuse_lora: the adapter is kept in factors and applied at run time on purpose -- the device weights are "
+                                  "derived layouts (stacked, interleaved, pre-split), a 16-bit merge loses the adapter's low bits, and the "
+                                  "scale changes per call.  There is nothing to fuse or unfuse")
+
+    unfuse_lora = fuse_lora
+
+    def set_adapters(self, *args, **kwargs):
+        raise NotImplementedError("set_adapters: one adapter at a time is implemented (unload_lora_weights() and load another); "
+                                  "cross_attention_kwargs={'scale': s} sets its weight per call")
+
+    def _apply_lora_scale(self, lora_scale):
+        """``cross_attention_kwargs["scale"]`` of THIS call into the scale table of every UNet that carries an adapter, before the
+        loop and outside any captured graph; ``_restore_lora_scale`` puts the models' own scale back when the call ends, so the key
+        holds for one call, as in diffusers.  Without the key a call runs at the model's own scale: 1.0, unless the user changed it
+        with ``unet.set_lora_scale``."""
+        self._lora_scale_restore = []
+        if lora_scale is None:
+            return
+        for name in ("unet", "gm_unet"):
+            u = getattr(self, name, None)
+            if u is not None and getattr(u, "has_lora", False):
+                self._lora_scale_restore.append((u, u._lora_scale))
+                u.set_lora_scale(float(lora_scale))
+
+    def _restore_lora_scale(self):
+        for u, s in getattr(self, "_lora_scale_restore", ()):
+            if u.has_lora:
+                u.set_lora_scale(s)
+        self._lora_scale_restore = []
 
     def _init_common(self, vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor,
                      image_encoder, requires_safety_checker, **extra_modules):
@@ -471,6 +536,7 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
         self._init_common(vae, text_encoder, tokenizer, unet, scheduler, safety_checker, feature_extractor, image_encoder,
                           requires_safety_checker)
 
+    @_per_call_lora_scale
     @torch.no_grad()
     def __call__(
         self,
@@ -521,6 +587,7 @@ class StableDiffusionGMPipeline(_GMPipelineBase):
             batch_size = prompt_embeds.shape[0]
         device = self._execution_device
         lora_scale = self.cross_attention_kwargs.get("scale", None) if self.cross_attention_kwargs is not None else None
+        self._apply_lora_scale(lora_scale)
         prompt_embeds, negative_prompt_embeds = self.encode_prompt(
             prompt, device, num_images_per_prompt, self.do_classifier_free_guidance, negative_prompt,
             prompt_embeds=prompt_embeds, negative_prompt_embeds=negative_prompt_embeds, lora_scale=lora_scale,

@@ -655,6 +655,27 @@ int gmd_dup_batch(const void* in, void* out, int64_t bytes, gmd_stream_t stream)
  * store; scales is a float32 DEVICE array.  out may alias a.  The combine of the composed decoupled cross-attention (added within
  * ABI v14). */
 int gmd_scaled_add(const void* a, const void* b, void* out, int dtype, int64_t n, const float* scales, int index, gmd_stream_t stream);
+/* A LoRA adapter applied at run time (added within ABI v14: one new entry point, no signature changed; csrc/lora.hip), GMD_BF16 /
+ * GMD_F16: the rank update of a projection's output as ONE launch,
+ *   Y[m, n] <- round( float(Y[m, n]) + scales[index] * sum_j T[m, j] * Bw[n, j] ),   T[m, j] = round( sum_k X[m, k] * Aw[j, k] )
+ * Both sums in float32 on the matrix cores, T rounded ONCE to `dtype` between them (what a 16-bit PEFT model does between lora_A and
+ * lora_B), the scale applied in float32 to the second sum, one rounding on the store.
+ *   X  [M, K], row stride ldx (>= K), K % 64 == 0;   Aw [Rp, K];   Bw [N, Rp]
+ *   Rp: the rank zero-padded by the host to a multiple of 32, at most 128 (true ranks 1..128)
+ *   transposed == 0: Y [M, N], row stride ldy >= N, N % 8 == 0 (ldy > N: a column range of a wider buffer, through a pointer offset);
+ *                    batch / tokens / strideY are ignored
+ *   transposed != 0: Y [batch, N, ldy] with the token contiguous (a V^T: gmd_gemm_qkv_vt's second output, the cached cross-attention
+ *                    vt), M == batch * tokens, row m = b * tokens + tok lands at Y[b * strideY + n * ldy + tok]; ldy >= tokens rounded
+ *                    up to 8, strideY >= N * ldy
+ * Nothing outside rows [0, M) x columns [0, N) -- transposed: tokens [0, tokens) of each row -- is written; every element is written by
+ * exactly one lane, once (no atomics), and a row's result does not depend on what else is in the launch.  scales: float32 DEVICE array
+ * read by the kernel (the convention of gmd_scaled_add), so a captured graph serves every scale.  M == 0: GMD_OK, nothing written.
+ * GMD_ERR_INVALID before a launch: X overlapping Y, pointers not 16-byte aligned, ldx / ldy / strideY not multiples of 8, K % 64,
+ * Rp % 32, Rp > 128, a NULL scales, X or one batch entry of Y beyond 2 GiB (32-bit byte offsets through buffer descriptors).
+ * GMD_F32 and the split dtypes: GMD_ERR_UNSUPPORTED (the caller composes gmd_gemm_nt twice and gmd_scaled_add). */
+int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N,
+                    int64_t ldx, int64_t ldy, int transposed, int batch, int tokens, int64_t strideY,
+                    const float* scales, int index, gmd_stream_t stream);
 /* elementwise cast between F32 and BF16 */
 int gmd_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, gmd_stream_t stream);
 
