@@ -310,8 +310,10 @@ extern "C" int gmd_wg_trace_set_ff_fused(void*);
 extern "C" int gmd_wg_trace_set_latent_step(void*);
 extern "C" int gmd_wg_trace_set_controlnet(void*);
 extern "C" int gmd_wg_trace_set_lora(void*);
+extern "C" int gmd_wg_trace_set_freeu(void*);
 extern "C" int gmd_wg_trace_enable(void* ring) {
     return gmd_wg_trace_set_gemm(ring) | gmd_wg_trace_set_attention(ring) | gmd_wg_trace_set_attention_ip(ring) | gmd_wg_trace_set_norm(ring) | gmd_wg_trace_set_ff_fused(ring) |
-           gmd_wg_trace_set_latent_step(ring) | gmd_wg_trace_set_elementwise(ring) | gmd_wg_trace_set_controlnet(ring) | gmd_wg_trace_set_lora(ring);
+           gmd_wg_trace_set_latent_step(ring) | gmd_wg_trace_set_elementwise(ring) | gmd_wg_trace_set_controlnet(ring) | gmd_wg_trace_set_lora(ring) |
+           gmd_wg_trace_set_freeu(ring);
 }
 #endif

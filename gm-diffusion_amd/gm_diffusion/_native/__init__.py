@@ -86,6 +86,7 @@ SIGNATURES = {
     "gmd_timestep_embedding_add": [P, P, P, I, I, I, I, F, P],
     "gmd_concat_channels": [P, I, P, I, P, I, L, P],
     "gmd_concat_channels_add": [P, I, P, I, P, I, P, I, P, L, P, I, L, P, I, P],
+    "gmd_concat_channels_freeu": [P, I, L, P, I, L, P, L, I, I, I, I, P, I, I, P],
     "gmd_silu": [P, I, L, P],
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
     "gmd_scaled_add": [P, P, P, I, L, P, I, P],

@@ -26,6 +26,7 @@ float32 NCHW taken from the fp32 accumulators of ``conv_out`` (never rounded to 
 """
 from __future__ import annotations
 
+import math
 import os
 
 import torch
@@ -323,6 +324,8 @@ class UNet2DConditionModel(_HipModule):
         self._lora_scale = 1.0    # ... set_lora_scale
         self._lora_id = 0         # ... identity of the loaded adapter (graph key, cross-attention K / V cache key)
         self._lora_version = 0    # ... bumped by load_lora / unload_lora / set_lora_scale: cached cross-attention K / V hold the scale
+        self._freeu = None        # FreeU: (s1, s2, b1, b2) of enable_freeu, None when off
+        self._freeu_dev = None    # ... the same four numbers as the float32 device table the kernel reads, built on first use
 
     # ------------------------------------------------------------------------------------------
     # structure
@@ -984,6 +987,62 @@ class UNet2DConditionModel(_HipModule):
         if self._lora_w is not None and self._lora_w_of is self._w:
             self._lora_w["scales"].copy_(self._lora_w["factors"] * scale)
 
+    # ------------------------------------------------------------------------------------------
+    # FreeU: diffusers' UNet2DConditionModel.enable_freeu / disable_freeu (hip_ops.concat_channels_freeu in up blocks 0 and 1)
+    # ------------------------------------------------------------------------------------------
+    def enable_freeu(self, s1, s2, b1, b2, **unsupported):
+        """FreeU ("Free Lunch in Diffusion U-Net"), as diffusers' ``enable_freeu``: in front of EVERY resnet of up blocks 0 and 1 the
+        first half of the backbone channels is scaled by ``b1`` / ``b2`` and the skip goes through the Fourier filter that scales its
+        lowest frequencies (threshold 1) by ``s1`` / ``s2``.  The skip concat of those six sites becomes ONE launch of
+        ``hip_ops.concat_channels_freeu``; nothing else changes, no weight is touched, no extra UNet evaluation.
+
+        All four values must be finite and > 0 (``ValueError`` naming the argument otherwise).  diffusers silently DISABLES FreeU when
+        one of them is 0 (its up blocks test the attributes for truth); here that is refused -- call ``disable_freeu()``.
+
+        The numbers live in one float32 device table the kernel reads: new numbers on an already-enabled model rewrite the table
+        (outside any graph capture) and keep every captured graph.  Enabling changes the launches, so captured forwards of the enabled
+        model are kept under a key with ("freeu",).  Not built: a filter threshold other than 1 (diffusers never passes another), the
+        FreeU authors' "v2" backbone map, per-block settings, FreeU on the VAE or a ControlNet."""
+        if unsupported:
+            raise NotImplementedError(f"enable_freeu: unsupported arguments {sorted(unsupported)}: only diffusers' (s1, s2, b1, b2) is "
+                                      "implemented -- no filter threshold other than 1, no 'v2' backbone map, no per-block settings")
+        vals = []
+        for name, v in (("s1", s1), ("s2", s2), ("b1", b1), ("b2", b2)):
+            if isinstance(v, (list, tuple, dict)) or torch.is_tensor(v) and v.numel() != 1:
+                raise NotImplementedError(f"enable_freeu: {name} must be one number (per-block settings are not implemented)")
+            v = float(v)
+            if not math.isfinite(v) or v <= 0.0:
+                raise ValueError(f"enable_freeu: {name}={v!r} must be finite and > 0 (diffusers treats 0 as 'FreeU off': call disable_freeu())")
+            vals.append(v)
+        if self._capturing:
+            raise HipExtensionError("the FreeU setting must be changed outside graph capture")
+        self._freeu = tuple(vals)
+        if self._freeu_dev is not None:
+            self._freeu_dev.copy_(torch.tensor(self._freeu, dtype=torch.float32))
+        return self
+
+    def disable_freeu(self):
+        """Back to the UNet without FreeU: the launches, and so the outputs, of a model that never had it."""
+        if self._capturing:
+            raise HipExtensionError("the FreeU setting must be changed outside graph capture")
+        self._freeu = None
+        self._graphs = {k: g for k, g in self._graphs.items() if ("freeu",) not in k}
+        return self
+
+    @property
+    def freeu(self):
+        """(s1, s2, b1, b2) of ``enable_freeu``, or None."""
+        return self._freeu
+
+    def _freeu_table(self):
+        """The float32 device table [s1, s2, b1, b2] (hip_ops.FREEU_PARAMS entries) the kernel reads, on this model's device."""
+        if self._freeu_dev is None or self._freeu_dev.device != self._t_dev.device:
+            if self._capturing:
+                raise HipExtensionError("the FreeU table must exist before graph capture")
+            self._freeu_dev = torch.tensor(self._freeu, dtype=torch.float32).to(self._t_dev.device)
+            assert self._freeu_dev.numel() == ops.FREEU_PARAMS
+        return self._freeu_dev
+
     def _ensure_lora(self):
         """The adapter's factors in kernel layouts, next to (and for) the prepared UNet weights: the rank zero-padded to the multiple
         the contractions of this dtype mode need, ``a`` a W operand (pre-split where the weights are), ``b`` a W operand for the plain
@@ -1310,16 +1369,23 @@ class UNet2DConditionModel(_HipModule):
             if len(c_down) != len(skips) or len(skips) + 1 != ops.CONTROL_RESIDUALS:
                 raise HipExtensionError(f"control: {len(c_down)} down residuals for {len(skips)} skips (the fused concat indexes "
                                         f"{ops.CONTROL_RESIDUALS} scales: twelve skips and the mid block)")
-        for blk in w["up"]:
+        fu = self._freeu_table() if self._freeu is not None else None
+        for i, blk in enumerate(w["up"]):
+            fu_i = fu if i < 2 else None  # diffusers: the up blocks of resolution_idx 0 and 1, in front of each of their resnets
             for j, r in enumerate(blk["res"]):
                 s, _, _ = skips.pop()
-                if control is None:
+                if control is None and fu_i is not None:  # table [s1, s2, b1, b2]: stage i scales the backbone by b_i, filters with s_i
+                    xs = ops.concat_channels_freeu(x, s, B, H, W, fu_i, 2 + i, i)
+                elif control is None:
                     xs = ops.concat_channels(x, s)
                 else:  # skip + residual where the skip is read; the mid residual rides on x in the first of them (used once)
                     k = len(skips)
                     xs = ops.concat_channels_add(x, s, ra=c_mid, rb=c_down[k], ia=ops.CONTROL_RESIDUALS - 1, ib=k, scales=c_scales,
                                                  r_row0=c_skip * H * W, hw=H * W if self._wants_colstats(H, W) else None)
                     c_mid = None
+                    if fu_i is not None:  # diffusers adds the residuals before the up blocks: the filter sees the sums -- in place
+                        ca = x.shape[-1]
+                        xs = ops.concat_channels_freeu(xs[..., :ca], xs[..., ca:], B, H, W, fu_i, 2 + i, i, out=xs)
                 x = self._resnet(r, xs, B, H, W, temb, eps)
                 if "attn" in blk:
                     x = self._transformer(blk["attn"][j], x, B, H, W, ehs, ip=ip)
@@ -1368,6 +1434,9 @@ class UNet2DConditionModel(_HipModule):
         if self._lora_raw is not None:  # the graph holds the adapter's launches and reads its factors and its table of scales
             self._ensure_lora()
             key += (("lora", self._lora_id),)
+        if self._freeu is not None:  # other launches; the numbers are read from the device table, so one graph serves every setting
+            self._freeu_table()
+            key += (("freeu",),)
         g = self._graphs.get(key)
         if g is not None:
             return g

@@ -25,7 +25,7 @@ from ._native import ACT_GEGLU, ACT_NONE, ACT_QUICK_GELU, ACT_SILU, GMD_BF16, GM
 __all__ = [
     "ACT_NONE", "ACT_SILU", "ACT_GEGLU", "ACT_QUICK_GELU", "embedding_lookup", "dpm_step", "dpm_sde_step", "ddpm_step", "ddim_step", "lcm_step", "euler_step", "lms_step", "unipc_step", "HipExtensionError", "dtype_code", "gemm_nt", "conv3x3", "conv3x3_tail", "pack_shortcut", "shortcut_fold_ok", "conv3x3_up2", "pack_upsample_phases", "upsample_phases_ok", "attention", "attention_ip", "scaled_add", "softmax_rows", "set_f32_mode", "f32_split", "split_weights", "scale_weight", "split_attention_ok", "ff_fused_ok", "ff_geglu_fused", "gemm_qkv_vt", "dup_batch",
     "groupnorm_scale_shift", "groupnorm_apply", "groupnorm", "groupnorm_split", "layernorm", "geglu", "timestep_embedding", "timestep_embedding_add",
-    "concat_channels", "concat_channels_add", "silu_", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
+    "concat_channels", "concat_channels_add", "concat_channels_freeu", "silu_", "cast", "pack_unet_input", "unpack_nchw", "latent_step", "cfg_std_ratio", "hdr_tail", "hdr_tail_resized", "prepare_sdr",
     "apply_gm_to_sdr", "tmo", "gamut_compress", "stage1_chain", "discretize_u16", "quantize_u8",
 ]
 
@@ -1205,6 +1205,69 @@ def concat_channels_add(a, b, ra=None, rb=None, ia=0, ib=0, scales=None, r_row0=
         tm.end("concat", 0.0, (2 * out.numel() + extra) * out.element_size(), t0)
     if sa is not None and sb is not None:
         out._colstats = [sa, sb]  # both parts' statistics describe what was stored: side by side, as concat_channels leaves them
+    return out
+
+
+# FreeU (diffusers' enable_freeu): the skip concat of one FreeU site as ONE launch (gmd_concat_channels_freeu).  The first half of the
+# backbone channels is scaled by params[ib]; the skip goes through diffusers' fourier_filter at threshold 1 -- X + (params[is] - 1) * low,
+# low = the inverse transform of the bins {0, -1} x {0, -1}, a seven-coefficient reduction per (sample, channel), no FFT.
+FREEU_PARAMS = 4  # the device table of UNet2DConditionModel.enable_freeu: [s1, s2, b1, b2]
+
+
+def _freeu_rows(t, rows, name):
+    """Row stride (elements) of ``t`` seen as [rows, C] channels-last: contiguous, or a column range of a wider contiguous buffer."""
+    c = t.shape[-1]
+    try:
+        v = t.view(rows, c)
+    except RuntimeError:
+        v = None
+    if v is None or (c > 1 and v.stride(1) != 1):
+        raise HipExtensionError(f"concat_channels_freeu: {name} must hold {rows} channels-last rows with one row stride "
+                                f"(got {tuple(t.shape)}, strides {t.stride()})")
+    return v.stride(0) if rows > 1 else c
+
+
+def concat_channels_freeu(a, s, B, H, W, params, ib, is_, out=None):
+    """``cat([a[..., :Ca/2] * params[ib], a[..., Ca/2:], fourier_filter(s, threshold=1, scale=params[is_])], -1)`` over the channels-last
+    rows of ``B`` samples of ``H x W`` pixels, one launch (gmd_concat_channels_freeu); float32 inside, one rounding per element.
+    ``params``: float32 device tensor read by the kernel, so a captured graph serves every setting.  ``out``: None (a new tensor), or
+    the result buffer -- which may be the very buffer ``a`` and ``s`` are the column views ``[..., :Ca]`` / ``[..., Ca:]`` of (in place,
+    behind ``concat_channels_add``).  The result carries no ``_colstats``: the producers' statistics describe neither part any more, so
+    the following GroupNorm takes its general route."""
+    for t in (a, s, params, out):
+        if t is not None and not t.is_cuda:
+            raise HipExtensionError(
+                "gm_diffusion (MI355X build): tensor is on %s; the compute path is hand-written HIP and has no CPU fallback" % t.device)
+    if is_asplit(a) or is_asplit(s):
+        raise HipExtensionError("concat_channels_freeu: an input is a pre-split activation (only contractions read that layout)")
+    B, H, W = int(B), int(H), int(W)
+    if B < 0 or H < 1 or W < 1:
+        raise HipExtensionError(f"concat_channels_freeu: bad sizes B={B}, H={H}, W={W}")
+    if a.dtype != s.dtype:
+        raise HipExtensionError(f"concat_channels_freeu: dtype mismatch {a.dtype} / {s.dtype}")
+    rows = B * H * W
+    ca, cs = a.shape[-1], s.shape[-1]
+    lda, lds = _freeu_rows(a, rows, "a"), _freeu_rows(s, rows, "s")
+    if params is None or params.dtype != torch.float32 or not params.is_contiguous():
+        raise HipExtensionError("concat_channels_freeu: params must be a contiguous float32 device tensor")
+    for i, nm in ((ib, "ib"), (is_, "is_")):
+        if not 0 <= int(i) < params.numel():
+            raise HipExtensionError(f"concat_channels_freeu: {nm}={i} outside [0, {params.numel()})")
+    if out is None:
+        out = torch.empty(a.shape[:-1] + (ca + cs,), dtype=a.dtype, device=a.device)
+    elif out.dtype != a.dtype or out.shape[-1] < ca + cs or out.shape[:-1] != a.shape[:-1]:
+        raise HipExtensionError(f"concat_channels_freeu: out {tuple(out.shape)} of {out.dtype} does not hold {tuple(a.shape[:-1])} rows of "
+                                f"{ca + cs} channels of {a.dtype}")
+    ldo = _freeu_rows(out, rows, "out")
+    if rows == 1:  # a single row has no stride: the in-place form is then recognised by its pointers alone
+        lda = lds = ldo
+    tm, t0 = _timed("concat_freeu")
+    check(lib().gmd_concat_channels_freeu(_ptr(a), ca, lda, _ptr(s), cs, lds, _ptr(out), ldo, dtype_code(a.dtype), B, H, W, _ptr(params),
+                                          int(ib), int(is_), _stream()), "gmd_concat_channels_freeu")
+    if tm:  # the skip is read twice (coefficients, then the correction)
+        tm.end("concat_freeu", 16.0 * rows * cs, (2 * rows * (ca + cs) + rows * cs) * out.element_size(), t0)
+    if getattr(out, "_colstats", None) is not None:
+        del out._colstats
     return out
 
 

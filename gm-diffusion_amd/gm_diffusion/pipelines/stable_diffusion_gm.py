@@ -117,6 +117,19 @@ class _GMPipelineBase(DiffusionPipeline):
     _callback_tensor_inputs = ["latents", "prompt_embeds", "negative_prompt_embeds"]
     _ip_adapter_supported = False  # image prompts (ip_adapter_image / ip_adapter_image_embeds): the dual-UNet pipeline only
 
+    # ---- FreeU (diffusers' StableDiffusionMixin.enable_freeu / disable_freeu) -------------------------------------------------------
+    def enable_freeu(self, s1, s2, b1, b2):
+        """diffusers' ``enable_freeu``: FreeU on ``self.unet`` only, as the mixin does (the dual pipeline: the SDR UNet;
+        ``pipe.gm_unet.enable_freeu(...)`` adapts the GM UNet).  See ``UNet2DConditionModel.enable_freeu``: all four values finite and
+        > 0; a filter threshold other than 1, the "v2" variant, per-block settings and FreeU on the VAE or a ControlNet are not built."""
+        if not hasattr(self, "unet"):
+            raise ValueError("The pipeline must have `unet` for using FreeU.")
+        self.unet.enable_freeu(s1=s1, s2=s2, b1=b1, b2=b2)
+
+    def disable_freeu(self):
+        """diffusers' ``disable_freeu``: ``self.unet`` back to the launches of a model that never had FreeU."""
+        self.unet.disable_freeu()
+
     # ---- LoRA (diffusers' StableDiffusionLoraLoaderMixin, for LOCAL files; one adapter, kept in factors) ---------------------------
     def load_lora_weights(self, path_or_state_dict, weight_name=None, subfolder=None, ignore_unsupported=False, adapter_name=None, **kwargs):
         """diffusers' ``load_lora_weights`` for LOCAL files: a ``.safetensors`` file, a ``.bin`` / ``.pt`` torch pickle (read with

@@ -638,6 +638,32 @@ int gmd_concat_channels(const void* A, int Ca, const void* Bm, int Cb, void* out
 int gmd_concat_channels_add(const void* A, int Ca, const void* Ra, int ia, const void* Bm, int Cb, const void* Rb, int ib,
                             const float* scales, int64_t r_row0, void* out, int dtype, int64_t rows,
                             float* colstats_b, int colstats_bucket, gmd_stream_t stream);
+/* The skip-connection concat of one FreeU site (diffusers' enable_freeu) in ONE launch (added within ABI v14: one new entry point, no
+ * signature changed; csrc/freeu.hip), channels-last, GMD_F32 / GMD_BF16 / GMD_F16:
+ *   out[r, 0 : Ca/2]     = rnd(float(A[r, c]) * params[ib])
+ *   out[r, Ca/2 : Ca]    = A[r, c]
+ *   out[r, Ca : Ca + Cs] = rnd(float(S[r, c]) + (params[is] - 1) * low_{b,c}[y, x]),      row r = (b * H + y) * W + x
+ * low = the real part of the inverse transform of the skip's bins {0, -1} x {0, -1} (an axis of length 1: {0} alone; of length 2: both
+ * of its bins): diffusers' fourier_filter with threshold = 1 (the only value it passes) is X + (scale - 1) * low.  With th_y = 2 pi y / H,
+ * ph_x = 2 pi x / W and (u, v) over {0, 1}^2 (u = 1 only for H > 1, v = 1 only for W > 1):
+ *   c_uv = sum_{y,x} X cos(u th_y + v ph_x),  d_uv = sum_{y,x} X sin(u th_y + v ph_x)
+ *   low[y, x] = 1 / (H W) * sum_{u,v} (c_uv cos(u th_y + v ph_x) + d_uv sin(u th_y + v ph_x))
+ * All arithmetic in float32, rnd = ONE rounding to `dtype`.  The backbone half is bit for bit torch's `h * b` on a tensor of `dtype`
+ * with a float32 scalar; params[is] == 1 / params[ib] == 1 make that part a raw copy.
+ *   A [B*H*W, Ca] with row stride lda, S [B*H*W, Cs] with row stride lds, out with row stride ldo >= Ca + Cs (strides in elements)
+ *   params: float32 DEVICE array read by the kernel (the convention of gmd_scaled_add / gmd_lora_update: one captured graph serves every
+ *           setting); ib / is index it
+ * In place: out may be the buffer A and S are views of -- A == out, S == out + Ca, lda == lds == ldo (behind gmd_concat_channels_add:
+ * the filter must see skip + ControlNet residual).  Every element is read for the last time and written by the same lane, and all reads
+ * that feed a channel's coefficients complete before one of its elements is overwritten.  No atomics; the summation order depends on
+ * (H, W) only, so a sample's output is the same bits whatever else is in the launch.  Nothing outside rows [0, B*H*W) x columns
+ * [0, Ca + Cs) is written.  B == 0: GMD_OK, nothing written.
+ * GMD_ERR_INVALID before a launch: pointers not 16-byte aligned; Ca / 2, Cs or a stride not a multiple of 8 (16-bit) / 4 (float32); a
+ * stride smaller than its row; H < 1 or W < 1; a NULL params or a negative index; a tensor beyond 2 GiB (32-bit byte offsets); A / S /
+ * out overlapping in any way other than the in-place form; H + W above 800 (16-bit) / 4496 (float32): the phase tables share the
+ * workgroup's 64 KB of LDS with the partial sums.  Not built: a threshold other than 1, the FreeU authors' "v2" backbone map. */
+int gmd_concat_channels_freeu(const void* A, int Ca, int64_t lda, const void* S, int Cs, int64_t lds, void* out, int64_t ldo,
+                              int dtype, int B, int H, int W, const float* params, int ib, int is, gmd_stream_t stream);
 /* X[i] = X[i] * sigmoid(X[i]) in place, n elements (a multiple of 8 (16-bit) / 4 (float32)), with the formula of the GroupNorm + SiLU
  * kernels (hardware reciprocal of 1 + exp(-x), float32 inside, one rounding on the store).  The ControlNet conditioning embedding's
  * activations, once per call (added within ABI v14). */
