@@ -519,6 +519,19 @@ int gmd_split_plan_ksplit(int M, int N, int K, int64_t workspace_bytes) {
     return f32_plan(M, N, K, 1, gmd_ws_usable_bytes(workspace_bytes), false).ksplit;
 }
 
+// Which kernel a float32 matrix-core launch takes: the planner calls of launch_split_any (gemm_split.hip), in its order.  A batched
+// launch gets no workspace (gmd_gemm_nt hands none over), so it never slices K.
+int gmd_split_plan_info(int dtype, int M, int N, int K, int batch, int64_t workspace_bytes, int geglu, int* out4) {
+    if (!(is_split(dtype) && M > 0 && N > 0 && K > 0 && K % BKS == 0 && batch > 0 && out4)) {
+        gmd_set_error("gmd_split_plan_info: float32 matrix-core launches only (GMD_F32S / GMD_F32SW / GMD_F32SA, K a multiple of %d)", BKS);
+        return GMD_ERR_INVALID;
+    }
+    const Plan pl = f32_plan(M, N, K, batch, batch == 1 ? gmd_ws_usable_bytes(workspace_bytes) : 0, geglu != 0);
+    const bool lc = dtype == GMD_F32SW && split_lc_fits(plan_config(), pl, M, N, K, batch);  // pre-split weights, plain activations
+    out4[0] = pl.bm; out4[1] = pl.bn; out4[2] = lc ? kLoaderConsumer : kRing; out4[3] = pl.ksplit;
+    return GMD_OK;
+}
+
 // 1 when a float32-split gmd_gemm_nt launch of these dimensions can take out_dtype = GMD_F32SA (store its result pre-split)
 int gmd_gemm_out_split_ok(int M, int N, int K, int geglu, int64_t workspace_bytes) {
     return f32_out_ok(M, N, K, geglu != 0, gmd_ws_usable_bytes(workspace_bytes));

@@ -351,6 +351,17 @@ def gemm_plan_info(dtype, M, N, K, batch=1, geglu=False):
     return tuple(out)
 
 
+def split_plan_info(code, M, N, K, batch=1, geglu=False):
+    """(tile rows, tile columns, kernel code, K slices) a float32 matrix-core launch of these dimensions takes; ``code``: GMD_F32S,
+    GMD_F32SW or GMD_F32SA (conv: M = B*Hout*Wout, N = Cout, K = 9*Cin); kernel code 0 = the ring kernel, 244 = the loader /
+    converter kernel.  For tests and measurement tools."""
+    import ctypes
+
+    out = (ctypes.c_int * 4)()
+    check(lib().gmd_split_plan_info(int(code), M, N, K, batch, WORKSPACE_BYTES, int(geglu), ctypes.addressof(out)), "gmd_split_plan_info")
+    return tuple(out)
+
+
 def stamp(buf, k, row=None):
     """Measurement only: write the device's 100 MHz counter into ``buf[row[0], k]`` (``buf``: int64 [rows, stride] device tensor,
     ``row``: int32 device scalar or None = row 0) at this point of the current stream -- also inside a graph capture (gmd_stamp)."""

@@ -443,6 +443,15 @@ int gmd_gemm_out_split_ok(int M, int N, int K, int geglu, int64_t workspace_byte
  * path does not take (K % 32 != 0).  Pure host function: tests use it to know what they exercise. */
 int gmd_split_plan_ksplit(int M, int N, int K, int64_t workspace_bytes);
 
+/* Which kernel a float32 matrix-core gmd_gemm_nt / gmd_gemm_qkv_vt / gmd_conv3x3 launch of these dimensions takes (`dtype`: GMD_F32S,
+ * GMD_F32SW or GMD_F32SA; for a convolution M = B*Hout*Wout, N = Cout, K = 9*Cin; `geglu` = 1 for GMD_ACT_GEGLU launches): out4 =
+ * {tile rows, tile columns, kernel code, K slices}, the twin of gmd_gemm_plan_info.  Kernel codes: 0 = the ring kernel, every wave
+ * splitting its own fragments (128x160, 128x128 or 64x64 tiles); 244 = the loader / converter kernel (128-row tiles, pre-split weights
+ * with a plain activation only, i.e. GMD_F32SW; off unless GMD_SPLIT_LC=1 or a plan override selects it).  K slices > 1: float32 slabs
+ * summed by a reduction launch (or by the fused GroupNorm).  A batched launch has no workspace and never slices.  Pure host
+ * function: tests use it to know what they exercise.  Returns GMD_ERR_INVALID for other element types or K % 32 != 0. */
+int gmd_split_plan_info(int dtype, int M, int N, int K, int batch, int64_t workspace_bytes, int geglu, int* out4);
+
 /* Debug facility like gmd_gemm_plan_override (refused unless the process has GMD_TUNING=1): how stride-1 gmd_conv3x3 launches on
  * 256-row ping-pong tiles fetch their activations -- 2 (the default) = the tile's input patch resident in LDS, continuous consumers;
  * 1 = patch resident, ping-pong consumers; 0 = the per-tap implicit GEMM.  Results agree to rounding (the K order differs).  Seeded

@@ -91,6 +91,28 @@ int main() {
         CHECK(split_lc_fits(lc, pl, 32768, 640, 2560, 1));
     }
 
+    // gmd_split_plan_info: the plan query of the float32 matrix-core launches answers what f32_plan + split_lc_fits answer
+    {
+        const int64_t whole = (96ll << 20) + kWsTail;
+        int o[4] = {-1, -1, -1, -1};
+        auto is = [&](int bm, int bn, int code, int ks) { return o[0] == bm && o[1] == bn && o[2] == code && o[3] == ks; };
+        for (int dtype : {GMD_F32S, GMD_F32SW, GMD_F32SA}) {
+            CHECK(gmd_split_plan_info(dtype, 4096, 1280, 64, 1, whole, 0, o) == GMD_OK && is(128, 160, 0, 1));     // 256 tiles
+            CHECK(gmd_split_plan_info(dtype, 4096, 1024, 64, 1, whole, 0, o) == GMD_OK && is(128, 128, 0, 1));
+            CHECK(gmd_split_plan_info(dtype, 300, 200, 320, 1, whole, 0, o) == GMD_OK && is(64, 64, 0, 1));
+            CHECK(gmd_split_plan_info(dtype, 256, 320, 2560, 1, whole, 0, o) == GMD_OK && is(128, 160, 0, 5));
+            CHECK(gmd_split_plan_info(dtype, 64, 320, 2048, 1, whole, 0, o) == GMD_OK && is(64, 64, 0, 4));
+            CHECK(gmd_split_plan_info(dtype, 4096, 1280, 10240, 1, whole, 0, o) == GMD_OK && is(128, 160, 0, 2));  // the reducer's second lap
+            CHECK(gmd_split_plan_info(dtype, 256, 320, 2560, 1, kWsTail, 0, o) == GMD_OK && is(64, 64, 0, 1));     // no usable workspace
+            CHECK(gmd_split_plan_info(dtype, 256, 320, 2560, 8, whole, 0, o) == GMD_OK && is(64, 64, 0, 1));       // batched: never sliced
+            CHECK(gmd_split_plan_info(dtype, 4096, 2560, 320, 1, whole, 1, o) == GMD_OK && is(128, 128, 0, 1));    // GEGLU: even TN
+            CHECK(gmd_split_plan_info(dtype, 4096, 1280, 48, 1, whole, 0, o) == GMD_ERR_INVALID);                  // K % 32
+            CHECK(gmd_split_plan_info(dtype, 4096, 1280, 64, 1, whole, 0, nullptr) == GMD_ERR_INVALID);
+        }
+        for (int dtype : {GMD_F32, GMD_BF16, GMD_F16, 6, -1}) CHECK(gmd_split_plan_info(dtype, 4096, 1280, 64, 1, whole, 0, o) == GMD_ERR_INVALID);
+        CHECK(gmd_split_plan_ksplit(256, 320, 2560, whole) == 5 && gmd_split_plan_ksplit(4096, 1280, 10240, whole) == 2);
+    }
+
     // in-kernel reduction: the loader-wave kernels only, up to fixup_max slices, never in front of a fused GroupNorm
     {
         const Plan pl{256, 160, kPingPong, 4};
@@ -129,6 +151,9 @@ int main() {
                                 const Plan f = f32_plan(M, N, K, batch, ws, geglu);
                                 check_plan(cfg, f, M, N, K, batch, ws);
                                 CHECK(f.pf == kRing && (!geglu || (f.ksplit == 1 && f.bn != 160)));
+                                int o4[4];
+                                CHECK(gmd_split_plan_info(GMD_F32SW, M, N, K, batch, whole, geglu, o4) == GMD_OK && o4[0] == f.bm && o4[1] == f.bn &&
+                                      o4[2] == 0 && o4[3] == f.ksplit);
                                 for (int mode : {-1, 1}) {
                                     PlanConfig lc = cfg;
                                     lc.split_lc_mode = mode;

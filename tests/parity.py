@@ -225,6 +225,65 @@ def unsplit(t):
     return v.permute(0, 1, 3, 2, 4).reshape(t.shape)                                       # element = 16 half + 4 q + j
 
 
+def split_store(x):
+    """float32 [..., C] (C % 32 == 0) -> the same values in the pre-split activation layout, held in a float32 tensor of the same shape:
+    the inverse of ``unsplit`` up to the split's residual (what gmd_store_split4 / gmd_split_weights write)."""
+    hi, lo = split_parts(x)
+    C = x.shape[-1]
+    h = torch.stack([hi, lo], 0).to(torch.float16).reshape(2, -1, C // 32, 2, 4, 4)  # [hi|lo, row, chunk, low|high 16, q, 4]
+    return h.permute(1, 2, 0, 4, 3, 5).contiguous().view(-1).view(torch.float32).reshape(x.shape)
+
+
+def presplit_read_bound(ref64, bound64):
+    """Bound of a result that was stored pre-split and read back through ``unsplit``: the bound of the float32 value v the kernel held
+    (|v - ref| <= bound) plus the split's own residual |v - (hi + lo)| <= 2^-22 |v| + 2^-25 (r_x of split_product_bound), with
+    |v| <= |ref| + bound."""
+    return bound64 + 2.0 ** -22 * (ref64.abs() + bound64) + 2.0 ** -25
+
+
+def split_layout_violations(t):
+    """Mask of the elements of a pre-split tensor (layout: see ``unsplit``) whose two halves are not a split: hi = f16(x) and
+    lo = f16(x - hi) give, for ANY x in float16's range,
+        |lo| <= 2^-11 |hi| (1 + 2^-10) + 2^-24
+    (round to nearest: |x - hi| <= half a unit in the last place of hi = 2^-11 2^e <= 2^-11 |hi| for a normal hi in [2^e, 2^(e+1));
+    lo rounds that difference once: a factor 1 + 2^-11; a subnormal hi has spacing 2^-24).  ``unsplit`` reads hi + lo, which
+    does not change when the two halves trade places -- a store that puts lo where hi belongs (or the halves of two different
+    pieces together) is invisible to a value check and is caught here: the swapped pair has |"lo"| = |hi| 2^11."""
+    C = t.shape[-1]
+    h = t.contiguous().view(torch.float16).reshape(-1, C // 32, 2, 4, 2, 4).to(torch.float64)
+    hi, lo = h[:, :, 0], h[:, :, 1]
+    bad = ~torch.isfinite(hi) | ~torch.isfinite(lo) | (lo.abs() > 2.0 ** -11 * hi.abs() * (1 + 2.0 ** -10) + 2.0 ** -24)
+    return bad.permute(0, 1, 3, 2, 4).reshape(t.shape)
+
+
+def im2col3x3(x, B, H, W, stride=1, upsample=False, pad_mode=0, out_size=None):
+    """The explicit [B Ho Wo, 9 C] operand of conv3x3 as the implicit-GEMM kernels walk it (include/gmd_hip.h, gmd_conv3x3): x is
+    [B, H W, C] channels-last, column k = tap * C + c with tap = 3 ky + kx, rows of ZEROS where a tap falls into the padding.  Modes:
+    stride 1 / 2 with padding 1; ``pad_mode=1``: stride 2 over the map padded by one row / column at the bottom / right only
+    (diffusers' Downsample2D with padding 0); ``upsample``: the nearest-2x image; ``out_size=(Ho, Wo)``: the nearest image of that
+    size, each side 2 in - 1 or 2 in (source index = destination >> 1 in both: for 2 in - 1, floor(d in / (2 in - 1)) = d >> 1 for every
+    d < 2 in - 1).  Pure indexing: the values are x's own, so the GEMM bounds apply to (im2col(x), w) unchanged.  Returns (matrix, Ho, Wo)."""
+    C = x.shape[-1]
+    xi = x.reshape(B, H * W, C)
+    if out_size is not None or upsample:
+        hv, wv = (int(out_size[0]), int(out_size[1])) if out_size is not None else (2 * H, 2 * W)
+        ho, wo, st, lo, up = hv, wv, 1, 1, True
+    elif pad_mode == 1:
+        hv, wv, ho, wo, st, lo, up = H, W, (H + 1 - 3) // 2 + 1, (W + 1 - 3) // 2 + 1, 2, 0, False
+    else:
+        hv, wv, ho, wo, st, lo, up = H, W, (H + 2 - 3) // stride + 1, (W + 2 - 3) // stride + 1, stride, 1, False
+    oy = torch.arange(ho, device=x.device).view(ho, 1, 1, 1)
+    ox = torch.arange(wo, device=x.device).view(1, wo, 1, 1)
+    ky = torch.arange(3, device=x.device).view(1, 1, 3, 1)
+    kx = torch.arange(3, device=x.device).view(1, 1, 1, 3)
+    vy, vx = oy * st + ky - lo, ox * st + kx - lo                        # position in the (virtual) image the taps walk
+    inside = (vy >= 0) & (vy < hv) & (vx >= 0) & (vx < wv)
+    sy, sx = (vy >> 1, vx >> 1) if up else (vy, vx)
+    idx = torch.where(inside, sy * W + sx, torch.full_like(sy * W + sx, H * W)).reshape(ho * wo * 9)  # H W = the zero row appended below
+    xz = torch.cat([xi, torch.zeros(B, 1, C, dtype=x.dtype, device=x.device)], 1)
+    return xz[:, idx].reshape(B * ho * wo, 9 * C), ho, wo
+
+
 def split_matmul_emulation(a, w):
     """a @ w^T as the split kernels compute it: three float32-accumulated products of float16 halves."""
     ah, al = split_parts(a)

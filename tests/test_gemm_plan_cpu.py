@@ -76,6 +76,56 @@ def test_forced_plans_and_fixup_off_in_a_tuning_child(lib, table):
     assert plan_table.query(lib, *first[:4], table["workspaces"][first[5]], first[4]) == table["answers"][first[6]]
 
 
+def test_split_plan_info_names_the_float32_kernels(lib, table):
+    """gmd_split_plan_info: every case table of the float32 parity tests (tests/split_cases.py) plans as the tests name it, the K
+    slices agree with gmd_split_plan_ksplit and the full-rows predicate with gmd_gemm_out_split_ok over the whole grid, other element
+    types are refused -- and in a GMD_TUNING=1 child the override that selects the loader / converter kernel shows as code 244 for
+    pre-split weights with a plain activation only."""
+    import ctypes
+
+    import split_cases as S
+    from gm_diffusion import hip_ops as ops
+
+    def info(code, M, N, K, batch=1, ws=ops.WORKSPACE_BYTES, geglu=0):
+        out = (ctypes.c_int * 4)()
+        rc = lib.gmd_split_plan_info(code, M, N, K, batch, ws, geglu, ctypes.addressof(out))
+        return (rc, *out)
+
+    for name, (M, N, K, (bm, bn, ks)) in {**S.GEMM_CASES, S.SECOND_LAP[0]: S.SECOND_LAP[1:]}.items():
+        for code in S.FORM_CODE.values():
+            assert info(code, M, N, K) == (0, bm, bn, 0, ks), name
+            assert ops.split_plan_info(code, M, N, K) == (bm, bn, 0, ks)
+    for tile, (B, ci, co, maps, (bm, bn, ks)) in S.CONV_TILES.items():
+        for mode in S.MODES:
+            ho, wo = S.conv_inputs(tile, mode)[8:10]
+            assert info(4, B * ho * wo, co, 9 * ci) == (0, bm, bn, 0, ks), (tile, mode)
+    assert info(3, 128, 72, 128, batch=3) == (0, 64, 64, 0, 1) and info(3, 72, 128, 128, batch=3) == (0, 64, 64, 0, 1)
+    assert info(4, 300, 2560, 320, geglu=1) == (0, 64, 64, 0, 1) and info(4, 4096, 2560, 320, geglu=1) == (0, 128, 128, 0, 1)
+    for code in (0, 1, 2, 6):
+        assert info(code, 4096, 1280, 64)[0] == 1  # GMD_ERR_INVALID
+    assert info(4, 4096, 1280, 48)[0] == 1
+    for (M, N, K, batch, _), ws in ((s, w) for s in plan_table.grid_shapes() for w in table["workspaces"]):
+        rc, bm, bn, code, ks = info(4, M, N, K, batch, ws)
+        assert rc == 0 and code == 0 and (bm, bn) in ((128, 160), (128, 128), (64, 64))
+        if batch == 1:
+            assert ks == lib.gmd_split_plan_ksplit(M, N, K, ws)
+            full = bm == 128 and ks == 1 and M % 128 == 0 and N % bn == 0
+            assert bool(lib.gmd_gemm_out_split_ok(M, N, K, 0, ws)) == full
+        else:
+            assert ks == 1
+    child = ("import sys, json; sys.path[:0] = [%r, %r]\n"
+             "from gm_diffusion import hip_ops as ops\nfrom gm_diffusion._native import lib\n"
+             "assert lib().gmd_gemm_plan_override(0, 0, 244, 0) == 0\n"
+             "print(json.dumps([ops.split_plan_info(c, *s) for c in (3, 4, 5) for s in ((4100, 1280, 128), (4100, 1288, 128), (4100, 1280, 96), (300, 200, 320))]))\n"
+             % (ROOT, os.path.join(ROOT, "gm-diffusion_amd")))
+    out = subprocess.run([sys.executable, "-c", child], env=dict(os.environ, GMD_TUNING="1"), capture_output=True, text=True, timeout=120)
+    assert out.returncode == 0, out.stderr[-2000:]
+    ring = [[128, 160, 0, 1], [128, 128, 0, 1], [128, 160, 0, 1], [64, 64, 0, 1]]
+    lc = [[128, 160, 244, 1], [128, 128, 244, 1], [128, 160, 0, 1], [64, 64, 0, 1]]  # (fewer than four K steps, 64-row tiles: the ring kernel)
+    assert json.loads(out.stdout) == ring + lc + ring
+    assert ops.split_plan_info(4, 4100, 1280, 128) == (128, 160, 0, 1)  # nothing leaked into this process
+
+
 def test_unexposed_planner_decisions_under_sanitizers(tmp_path):
     """tests/gemm_plan_check.cpp + gemm_plan.cpp + gmd_error.cpp, built by the host compiler with AddressSanitizer and
     UndefinedBehaviorSanitizer and run as a program of its own: known answers of pick_tile_group / conv_channel_block / conv_patch_ok /

@@ -32,6 +32,20 @@ def test_lap_constants_quote_the_grid_caps():
         assert cap and cap.group(1) == cap.group(2), name
         assert re.search(r"constexpr int kThreads = 256;", src), name
         assert eval(cap.group(1)) * 256 == lap, (name, cap.group(1), lap)
+    # the float32 slab reducer (tests/split_cases.py LAP_REDUCE; tests/test_split_parity_gpu.py asserts the second lap's rows): one
+    # thread per four columns, the grid capped where launch_split_any launches it
+    import split_cases
+
+    src = open(os.path.join(CSRC, "gemm_split.hip")).read()
+    launch = src[src.index("int launch_split_any"):]
+    m = re.search(r"const int64_t total = \(int64_t\)p\.M \* \(\(p\.N \+ 3\) / 4\);\s*int64_t g = \(total \+ (\d+)\) / (\d+);\s*if \(g > (\d+)\) g = (\d+);\s*"
+                  r"splitk_reduce_f32_kernel<<<\(int\)g, (\d+), 0, s>>>", launch)
+    assert m and m.group(3) == m.group(4) and int(m.group(1)) + 1 == int(m.group(2)) == int(m.group(5)), "the reducer's launch moved"
+    assert (int(m.group(3)), int(m.group(5))) == (split_cases.REDUCE_GRID_CAP, split_cases.REDUCE_THREADS)
+    assert split_cases.LAP_REDUCE == int(m.group(3)) * int(m.group(5)) == 1 << 20
+    assert "i += (int64_t)gridDim.x * blockDim.x" in src[src.index("void splitk_reduce_f32_kernel"):src.index("// ring kernel:")]
+    M, N = split_cases.SECOND_LAP[1:3]
+    assert split_cases.reducer_lap_start(M, N) == (3276, 1024) and split_cases.reducer_lap_start(4096, 1024) is None
 
 
 # ---- second lap: never written / first lap's sample index ----
