@@ -7,9 +7,9 @@ namespace {
 
 constexpr int kThreads = 256;
 
-__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
-
-template <typename T>
+// IL: X's columns in the layout the fused GEGLU projections produce (value columns 0-15, gate columns 0-15, value 16-31, ...: the
+// ff1 weight rows interleaved in groups of 16) instead of [value half | gate half]
+template <typename T, bool IL>
 __global__ __launch_bounds__(kThreads) void geglu_kernel(const T* __restrict__ X, T* __restrict__ Y, int64_t rows, int F) {
     GMD_WG_TRACE_SCOPE(WGK_OTHER);
     constexpr int V = Elem<T>::kVec;
@@ -19,8 +19,9 @@ __global__ __launch_bounds__(kThreads) void geglu_kernel(const T* __restrict__ X
         const int64_t r = i / FV;
         const int f = (int)(i - r * FV) * V;
         float h[V], g[V];
-        load_vec(X + r * 2 * F + f, h);
-        load_vec(X + r * 2 * F + F + f, g);
+        const int fv = IL ? 32 * (f >> 4) + (f & 15) : f;  // V divides 16: a piece never straddles a group
+        load_vec(X + r * 2 * F + fv, h);
+        load_vec(X + r * 2 * F + (IL ? 16 : F) + fv, g);
 #pragma unroll
         for (int j = 0; j < V; ++j) h[j] = h[j] * gelu_erf(g[j]);
         store_vec(Y + r * F + f, h);
@@ -159,9 +160,24 @@ int gmd_geglu(const void* X, void* Y, int dtype, int64_t rows, int F, gmd_stream
     GMD_REQUIRE(F % (gmd_is_half(dtype) ? 8 : 4) == 0, "gmd_geglu: F=%d must be a multiple of %d", F, gmd_is_half(dtype) ? 8 : 4);
     gmd_for_dtype(dtype, [&](auto tag) {
         using T = decltype(tag);
-        geglu_kernel<T><<<grid_for(rows * (F / Elem<T>::kVec)), kThreads, 0, s>>>((const T*)X, (T*)Y, rows, F);
+        geglu_kernel<T, false><<<grid_for(rows * (F / Elem<T>::kVec)), kThreads, 0, s>>>((const T*)X, (T*)Y, rows, F);
     });
     GMD_CHECK_LAUNCH("gmd_geglu");
+    return GMD_OK;
+}
+
+int gmd_geglu_interleaved(const void* X, void* Y, int dtype, int64_t rows, int F, gmd_stream_t stream) {
+    GMD_REQUIRE(rows >= 0 && F > 0, "gmd_geglu_interleaved: bad shape");
+    GMD_REQUIRE(gmd_known_dtype(dtype), "gmd_geglu_interleaved: bad dtype %d", dtype);
+    GMD_REQUIRE(F % 16 == 0, "gmd_geglu_interleaved: F=%d must be a multiple of 16 (the interleave group)", F);
+    if (rows == 0) return GMD_OK;
+    GMD_REQUIRE(X && Y && gmd_aligned16(X) && gmd_aligned16(Y), "gmd_geglu_interleaved: null or unaligned pointer");
+    hipStream_t s = (hipStream_t)stream;
+    gmd_for_dtype(dtype, [&](auto tag) {
+        using T = decltype(tag);
+        geglu_kernel<T, true><<<grid_for(rows * (F / Elem<T>::kVec)), kThreads, 0, s>>>((const T*)X, (T*)Y, rows, F);
+    });
+    GMD_CHECK_LAUNCH("gmd_geglu_interleaved");
     return GMD_OK;
 }
 

@@ -171,6 +171,9 @@ static inline void gmd_for_dtype(int dtype, F&& f) {
 // FMAs, v_div_fmas, v_div_fixup: 12 instructions per element): GroupNorm + SiLU runs this on every element of every resnet input.
 __device__ __forceinline__ float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.0f + __expf(-x)); }
 
+// x * Phi(x), the erf form (GEGLU.forward of diffusers with approximate="none"): gmd_geglu and the LoRA GEGLU launch share it
+__device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
+
 // ---- float32 -> (hi, lo) float16 pairs: x = hi + lo, hi = f16(x), lo = f16(x - hi) (gemm_split.hip) ----
 typedef __attribute__((ext_vector_type(2))) _Float16 gmd_f16x2_t;
 // (a, b) -> packed f16 pair hi and packed f16 pair lo

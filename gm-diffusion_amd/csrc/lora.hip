@@ -18,6 +18,16 @@
 //     of the work).  No atomics: every element of Y is written by exactly one lane, once.  Summation orders depend on k and j only,
 //     never on the grid: a row's result is the same bits whatever else is in the launch.
 // The scale is read from DEVICE memory (one wave-uniform load), so one captured graph serves every scale.
+//
+// The update of a feed-forward's first projection and its GEGLU as ONE launch (gmd_lora_geglu, MODE_GEGLU of the same kernel):
+//   F[m, f] = round( v * gelu_erf(g) ),  v = float(Y[m, value(f)]) + s U[m, value(f)],  g = float(Y[m, gate(f)]) + s U[m, gate(f)]
+// Y [M, N = 8C] is the pre-activation in the layout the interleaved ff1 weight produces: in a tile of 64 columns, columns 0-15 and
+// 32-47 are the values of outputs 32 t .. 32 t + 31, columns 16-31 and 48-63 their gates; Bw's rows are in the same order.  Phase 1
+// is the one above.  Phase 2 walks Y in those tiles; a tile takes four MFMA chains per wave (value / gate x two halves of its
+// 32 outputs).  The A operand takes ANY row of the staged Bw tile on a given lane: chain (vg, q) is fed, on lane c, the Bw row of
+// output f = 8 (c >> 2) + 4 q + (c & 3), so lane (c, g) holds value AND gate of the 8 CONSECUTIVE outputs 8 g .. 8 g + 7 of row
+// 16 wid + c: two 16-byte loads of Y (whose 8 values and 8 gates are contiguous), one 16-byte store of F.  Y is read once and never
+// written, every element of F is written once by one lane; v, g, the GELU and the product stay in float32.
 #include "gmd_common.h"
 
 namespace {
@@ -28,24 +38,28 @@ struct LoraParams {
     const bf16_t* X;
     const bf16_t* Aw;
     const bf16_t* Bw;
-    bf16_t* Y;
+    bf16_t* Y;           // MODE_GEGLU: read-only
+    bf16_t* F;           // MODE_GEGLU only: the output [M, N / 2], row stride ldf
     const float* scale;  // the entry this launch reads (array base + index)
     int M, K, N;
     int tokens, tblocks;  // transposed mode: tokens per batch entry, 64-token blocks per batch entry
-    int ldx, ldy;         // elements
+    int ldx, ldy, ldf;    // elements
     int64_t strideY;      // transposed mode: elements between batch entries of Y
     int tiles_per_y;      // N tiles of 64 columns one workgroup walks
-    unsigned xbytes, ybytes;
+    unsigned xbytes, ybytes, fbytes;
 };
+
+enum { MODE_PLAIN = 0, MODE_TRANS = 1, MODE_GEGLU = 2 };
 
 constexpr int ROWS = 64;  // rows of X per workgroup
 constexpr int NT = 64;    // columns of Y per tile
 constexpr int KT = 64;    // K step
 constexpr int AROW = KT * 2 + 16;  // bytes per LDS row of an Aw tile: 36 dwords, conflict-free 16-byte row reads
 
-template <typename HT, int RP, bool TRANS>
+template <typename HT, int RP, int MODE>
 __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
     GMD_WG_TRACE_SCOPE(WGK_OTHER);
+    constexpr bool TRANS = MODE == MODE_TRANS;
     constexpr int NJ = RP / 16;        // 16-wide blocks of the rank
     constexpr int NK2 = RP / 32;       // k-steps of the second product; also 16-byte staging chunks per thread and tile
     constexpr int TROW = RP * 2 + 16;  // bytes per LDS row of That and of a Bw tile: 20 / 36 / 52 / 68 dwords, conflict-free 16-byte row reads
@@ -124,6 +138,83 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
         w.x = Half<HT>::pack2(tacc[jb][0], tacc[jb][1]);
         w.y = Half<HT>::pack2(tacc[jb][2], tacc[jb][3]);
         *reinterpret_cast<uint2*>(Ts + xr * TROW + (16 * jb + 4 * g) * 2) = w;
+    }
+
+    if constexpr (MODE == MODE_GEGLU) {
+        // ---- phase 2 of the GEGLU launch: the walk over the 64-column tiles of Y (N % 64 == 0: every tile and every Bw row exists) ----
+        const int t_begin = blockIdx.y * p.tiles_per_y, t_end = min(p.N / NT, t_begin + p.tiles_per_y);
+        u32x4 breg[NK2];
+        auto load_b = [&](int n0) {
+#pragma unroll
+            for (int u = 0; u < NK2; ++u) {
+                const int id = tid + 256 * u, row = id / (RP / 8), ch = id - row * (RP / 8);
+                breg[u] = *reinterpret_cast<const u32x4*>(p.Bw + (int64_t)(n0 + row) * RP + 8 * ch);
+            }
+        };
+        auto store_b = [&]() {
+#pragma unroll
+            for (int u = 0; u < NK2; ++u) {
+                const int id = tid + 256 * u, row = id / (RP / 8), ch = id - row * (RP / 8);
+                *reinterpret_cast<u32x4*>(stage + row * TROW + ch * 16) = breg[u];
+            }
+        };
+        if (t_begin < t_end) load_b(t_begin * NT);
+        __syncthreads();  // That complete; the stage is free
+
+        uint4 tf[NK2];  // That row xr, the B operand of every chain, held for the whole walk
+#pragma unroll
+        for (int ks = 0; ks < NK2; ++ks) tf[ks] = *reinterpret_cast<const uint4*>(Ts + xr * TROW + (32 * ks + 8 * g) * 2);
+        const float s = *p.scale;
+        const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p.Y, 0, (int)p.ybytes, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)p.F, 0, (int)p.fbytes, 0x00020000);
+        const bool valid = xr < rows_valid;
+        // unsigned: the row may lie beyond M (unused then)
+        const unsigned yrow = (unsigned)(row0 + xr) * (unsigned)p.ldy * 2u, frow = (unsigned)(row0 + xr) * (unsigned)p.ldf * 2u;
+
+        for (int t = t_begin; t < t_end; ++t) {
+            store_b();
+            __syncthreads();
+            load_b(min(t + 1, t_end - 1) * NT);  // the next tile into registers (the last tile loads its own again)
+            // outputs 32 t + 8 g .. + 7: their values at tile columns 32 (g >> 1) + 8 (g & 1) .., their gates 16 columns on
+            const unsigned yoff = yrow + (unsigned)(t * NT + 32 * (g >> 1) + 8 * (g & 1)) * 2u;
+            uint4 yv = make_uint4(0, 0, 0, 0), yg = make_uint4(0, 0, 0, 0);
+            if (valid) {
+                yv = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rsY, (int)yoff, 0, 0));
+                yg = as_u4(__builtin_amdgcn_raw_buffer_load_b128(rsY, (int)(yoff + 32u), 0, 0));
+            }
+            f32x4 acc[2][2];  // [value / gate][q]: element i of chain q is output 8 g + 4 q + i
+#pragma unroll
+            for (int vg = 0; vg < 2; ++vg)
+#pragma unroll
+                for (int q = 0; q < 2; ++q) {
+                    acc[vg][q] = f32x4{0.f, 0.f, 0.f, 0.f};
+                    const int f = 8 * (c >> 2) + 4 * q + (c & 3);
+                    const int brow = 32 * (f >> 4) + (f & 15) + 16 * vg;
+#pragma unroll
+                    for (int ks = 0; ks < NK2; ++ks) {
+                        const uint4 bf = *reinterpret_cast<const uint4*>(stage + brow * TROW + (32 * ks + 8 * g) * 2);
+                        acc[vg][q] = Half<HT>::mfma16(bf, tf[ks], acc[vg][q]);
+                    }
+                }
+            if (valid) {
+                const unsigned wv[4] = {yv.x, yv.y, yv.z, yv.w}, wg[4] = {yg.x, yg.y, yg.z, yg.w};
+                unsigned o[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    float vlo, vhi, glo, ghi;
+                    Half<HT>::unpack2(wv[e], vlo, vhi);
+                    Half<HT>::unpack2(wg[e], glo, ghi);
+                    const f32x4& av = acc[0][e >> 1];
+                    const f32x4& ag = acc[1][e >> 1];
+                    const int i = 2 * (e & 1);
+                    o[e] = Half<HT>::pack2((vlo + s * av[i]) * gelu_erf(glo + s * ag[i]), (vhi + s * av[i + 1]) * gelu_erf(ghi + s * ag[i + 1]));
+                }
+                __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, make_uint4(o[0], o[1], o[2], o[3])), rsF,
+                                                       (int)(frow + (unsigned)(t * (NT / 2) + 8 * g) * 2u), 0, 0);
+            }
+            __syncthreads();  // the tile is consumed: the next store_b may overwrite it
+        }
+        return;
     }
 
     // ---- phase 2: the walk over N ----
@@ -231,8 +322,8 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
 
 template <typename HT, int RP>
 int launch_lora(const LoraParams& p, bool trans, dim3 grid, hipStream_t s) {
-    if (trans) lora_update_kernel<HT, RP, true><<<grid, 256, 0, s>>>(p);
-    else lora_update_kernel<HT, RP, false><<<grid, 256, 0, s>>>(p);
+    if (trans) lora_update_kernel<HT, RP, MODE_TRANS><<<grid, 256, 0, s>>>(p);
+    else lora_update_kernel<HT, RP, MODE_PLAIN><<<grid, 256, 0, s>>>(p);
     GMD_CHECK_LAUNCH("gmd_lora_update");
     return GMD_OK;
 }
@@ -247,7 +338,74 @@ int dispatch_lora(const LoraParams& p, int Rp, bool trans, dim3 grid, hipStream_
     }
 }
 
+template <typename HT>
+int dispatch_lora_geglu(const LoraParams& p, int Rp, dim3 grid, hipStream_t s) {
+    switch (Rp) {
+        case 32: lora_update_kernel<HT, 32, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
+        case 64: lora_update_kernel<HT, 64, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
+        case 96: lora_update_kernel<HT, 96, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
+        default: lora_update_kernel<HT, 128, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
+    }
+    GMD_CHECK_LAUNCH("gmd_lora_geglu");
+    return GMD_OK;
+}
+
+// N tiles of 64 columns one workgroup walks: N is split over gridDim.y where the row blocks alone cannot fill the chip (256 CUs,
+// several workgroups each); That is recomputed per split
+int tiles_per_y(int64_t gx, int ntiles) {
+    int nsplit = (int)((512 + gx - 1) / gx);
+    if (nsplit > ntiles) nsplit = ntiles;
+    if (nsplit < 1) nsplit = 1;
+    return (ntiles + nsplit - 1) / nsplit;
+}
+
 }  // namespace
+
+extern "C" int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                              int64_t ldx, int64_t ldy, int64_t ldf, const float* scales, int index, gmd_stream_t stream) {
+    if (dtype != GMD_BF16 && dtype != GMD_F16) {
+        gmd_set_error("gmd_lora_geglu: GMD_BF16 / GMD_F16 are implemented (float32 composes gmd_gemm_nt twice, gmd_scaled_add and "
+                      "gmd_geglu / gmd_geglu_interleaved)");
+        return GMD_ERR_UNSUPPORTED;
+    }
+    GMD_REQUIRE(M >= 0 && C > 0, "gmd_lora_geglu: bad shape M=%d C=%d", M, C);
+    GMD_REQUIRE(C % 64 == 0, "gmd_lora_geglu: C=%d must be a multiple of 64", C);
+    GMD_REQUIRE(C <= (1 << 24), "gmd_lora_geglu: C=%d too large", C);
+    GMD_REQUIRE(Rp > 0 && Rp % 32 == 0, "gmd_lora_geglu: padded rank Rp=%d must be a positive multiple of 32", Rp);
+    GMD_REQUIRE(Rp <= 128, "gmd_lora_geglu: padded rank Rp=%d above 128", Rp);
+    GMD_REQUIRE(scales != nullptr && index >= 0, "gmd_lora_geglu: scales must be a device array, the index non-negative");
+    const int N = 8 * C, NF = 4 * C;
+    GMD_REQUIRE(ldx >= C && ldy >= N && ldf >= NF, "gmd_lora_geglu: ldx=%lld / ldy=%lld / ldf=%lld smaller than C=%d / 8C / 4C", (long long)ldx,
+                (long long)ldy, (long long)ldf, C);
+    GMD_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && ldf % 8 == 0, "gmd_lora_geglu: leading dimensions must be multiples of 8");
+    if (M == 0) return GMD_OK;  // nothing to write
+    GMD_REQUIRE(X && Aw && Bw && Y && F, "gmd_lora_geglu: null pointer");
+    GMD_REQUIRE(gmd_aligned16(X) && gmd_aligned16(Aw) && gmd_aligned16(Bw) && gmd_aligned16(Y) && gmd_aligned16(F),
+                "gmd_lora_geglu: pointers must be 16-byte aligned");
+    const int64_t xbytes = (((int64_t)M - 1) * ldx + C) * 2, ybytes = (((int64_t)M - 1) * ldy + N) * 2, fbytes = (((int64_t)M - 1) * ldf + NF) * 2;
+    GMD_REQUIRE(xbytes < (1ll << 31) && ybytes < (1ll << 31) && fbytes < (1ll << 31), "gmd_lora_geglu: X, Y or F exceeds 2 GiB (32-bit byte offsets)");
+    {
+        const uintptr_t f0 = (uintptr_t)F, f1 = f0 + (uintptr_t)fbytes, x0 = (uintptr_t)X, x1 = x0 + (uintptr_t)xbytes, y0 = (uintptr_t)Y,
+                        y1 = y0 + (uintptr_t)ybytes;
+        GMD_REQUIRE(x1 <= f0 || f1 <= x0, "gmd_lora_geglu: F overlaps X");
+        GMD_REQUIRE(y1 <= f0 || f1 <= y0, "gmd_lora_geglu: F overlaps Y");
+    }
+    LoraParams p;
+    p.X = (const bf16_t*)X; p.Aw = (const bf16_t*)Aw; p.Bw = (const bf16_t*)Bw; p.Y = (bf16_t*)const_cast<void*>(Y);
+    p.F = (bf16_t*)F; p.ldf = (int)ldf; p.fbytes = (unsigned)fbytes;
+    p.scale = scales + index;
+    p.M = M; p.K = C; p.N = N;
+    p.tokens = M; p.tblocks = 0;
+    p.ldx = (int)ldx; p.ldy = (int)ldy;
+    p.strideY = 0;
+    p.xbytes = (unsigned)xbytes; p.ybytes = (unsigned)ybytes;
+    const int64_t gx = ((int64_t)M + ROWS - 1) / ROWS;
+    const int ntiles = N / NT;
+    p.tiles_per_y = tiles_per_y(gx, ntiles);
+    dim3 grid((unsigned)gx, (unsigned)((ntiles + p.tiles_per_y - 1) / p.tiles_per_y), 1);
+    hipStream_t s = (hipStream_t)stream;
+    return dtype == GMD_F16 ? dispatch_lora_geglu<f16_t>(p, Rp, grid, s) : dispatch_lora_geglu<bf16_t>(p, Rp, grid, s);
+}
 
 extern "C" int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N, int64_t ldx,
                                int64_t ldy, int transposed, int batch, int tokens, int64_t strideY, const float* scales, int index,
@@ -292,17 +450,13 @@ extern "C" int gmd_lora_update(const void* X, const void* Aw, const void* Bw, vo
     p.tblocks = (p.tokens + ROWS - 1) / ROWS;
     p.ldx = (int)ldx; p.ldy = (int)ldy;
     p.strideY = transposed ? strideY : 0;
+    p.F = nullptr; p.ldf = 0; p.fbytes = 0;
     p.xbytes = (unsigned)xbytes; p.ybytes = (unsigned)yslab;
     const int64_t gx = transposed ? (int64_t)batch * p.tblocks : ((int64_t)M + ROWS - 1) / ROWS;
     GMD_REQUIRE(gx < (1ll << 31), "gmd_lora_update: grid too large");
-    // split N where the row blocks alone cannot fill the chip (256 CUs, several workgroups each); That is recomputed per split
     const int ntiles = (N + NT - 1) / NT;
-    int nsplit = (int)((512 + gx - 1) / gx);
-    if (nsplit > ntiles) nsplit = ntiles;
-    if (nsplit < 1) nsplit = 1;
-    p.tiles_per_y = (ntiles + nsplit - 1) / nsplit;
-    nsplit = (ntiles + p.tiles_per_y - 1) / p.tiles_per_y;
-    dim3 grid((unsigned)gx, (unsigned)nsplit, 1);
+    p.tiles_per_y = tiles_per_y(gx, ntiles);
+    dim3 grid((unsigned)gx, (unsigned)((ntiles + p.tiles_per_y - 1) / p.tiles_per_y), 1);
     hipStream_t s = (hipStream_t)stream;
     return dtype == GMD_F16 ? dispatch_lora<f16_t>(p, Rp, transposed != 0, grid, s) : dispatch_lora<bf16_t>(p, Rp, transposed != 0, grid, s);
 }

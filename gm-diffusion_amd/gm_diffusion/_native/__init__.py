@@ -83,6 +83,7 @@ SIGNATURES = {
     "gmd_groupnorm_fused": [P, P, I, I, L, I, I, F, P, P, I, P],
     "gmd_layernorm": [P, P, I, L, I, P, P, F, P],
     "gmd_geglu": [P, P, I, L, I, P],
+    "gmd_geglu_interleaved": [P, P, I, L, I, P],
     "gmd_timestep_embedding": [P, P, I, I, I, I, F, P],
     "gmd_timestep_embedding_add": [P, P, P, I, I, I, I, F, P],
     "gmd_concat_channels": [P, I, P, I, P, I, L, P],
@@ -92,6 +93,7 @@ SIGNATURES = {
     "gmd_embedding_lookup": [P, P, P, P, I, L, I, I, I, P],
     "gmd_scaled_add": [P, P, P, I, L, P, I, P],
     "gmd_lora_update": [P, P, P, P, I, I, I, I, I, L, L, I, I, I, L, P, I, P],
+    "gmd_lora_geglu": [P, P, P, P, P, I, I, I, I, L, L, L, P, I, P],
     "gmd_cast": [P, I, P, I, L, P],
     "gmd_dup_batch": [P, P, L, P],
 }

@@ -13,9 +13,13 @@ what their loaders accept (diffusers ``LoraLoaderMixin.lora_state_dict`` and its
 A module's update is  W + scale * (alpha / r) * up @ down  (factor 1 without an alpha).  kohya names are resolved against the model's
 OWN module names with the dots replaced -- never by splitting on underscores, which ``to_out_0`` and ``transformer_blocks_0`` defeat.
 
-What the UNet applies (``SUPPORTED_SUFFIXES``): the eight attention projections of every BasicTransformerBlock -- the target set of
-diffusers' train_text_to_image_lora.py.  Everything else is refused BY NAME (``NotImplementedError``) unless ``ignore_unsupported``,
-which skips it with one warning listing the modules: a silently thinner adapter is never the default.
+What the UNet applies by default (``targets="attention"``, ``SUPPORTED_SUFFIXES``): the eight attention projections of every
+BasicTransformerBlock -- the target set of diffusers' train_text_to_image_lora.py.  ``targets="transformer"`` (opt-in) adds the
+other linears of a Transformer2DModel (``TRANSFORMER_SUFFIXES``): the feed-forward's ``ff.net.0.proj`` and ``ff.net.2`` and the
+transformer's ``proj_in`` / ``proj_out`` -- what kohya's default settings and PEFT's wider ``target_modules`` train; the 4-D factors
+kohya / LoCon write for a 1x1-convolution proj_in / proj_out are squeezed to matrices.  Everything else is refused BY NAME
+(``NotImplementedError``) unless ``ignore_unsupported``, which skips it with one warning listing the modules: a silently thinner
+adapter is never the default.
 """
 import re
 import warnings
@@ -25,6 +29,10 @@ import torch
 from ..hip_ops import LORA_MAX_RANK as MAX_RANK  # the kernel's limit; importing hip_ops needs no GPU
 
 SUPPORTED_SUFFIXES = tuple(f"{a}.{p}" for a in ("attn1", "attn2") for p in ("to_q", "to_k", "to_v", "to_out.0"))
+FF_SUFFIXES = ("ff.net.0.proj", "ff.net.2")
+PROJ_SUFFIXES = ("proj_in", "proj_out")
+TRANSFORMER_SUFFIXES = SUPPORTED_SUFFIXES + FF_SUFFIXES + PROJ_SUFFIXES
+TARGETS = ("attention", "transformer")
 
 # key fragments of adapter families that are no plain linear LoRA at all
 _FOREIGN = ("hada_", "lokr_", "dora_scale", "lora_mid", "lora_magnitude_vector")
@@ -37,16 +45,36 @@ _PARTS = ((".lora_A.weight", _DOWN), (".lora_B.weight", _UP), (".lora.down.weigh
 _PROCESSOR = re.compile(r"^(.*)\.processor\.(to_q|to_k|to_v|to_out)_lora\.(down|up)\.weight$")
 
 
-def supported(module):
-    """Is ``module`` one of the projections the UNet applies an adapter to?"""
-    return ".transformer_blocks." in module and module.endswith(SUPPORTED_SUFFIXES)
+def _check_targets(targets):
+    if targets not in TARGETS:
+        raise ValueError(f"LoRA: targets={targets!r} is not one of {TARGETS}")
+    return targets
+
+
+def _is_transformer_proj(module):
+    """proj_in / proj_out of a Transformer2DModel (``...attentions.N.proj_in``), not a module that merely ends alike."""
+    head, _, leaf = module.rpartition(".")
+    return leaf in PROJ_SUFFIXES and re.search(r"attentions\.\d+$", head) is not None
+
+
+def supported(module, targets="attention"):
+    """Is ``module`` one of the projections the UNet applies an adapter to under ``targets``?"""
+    _check_targets(targets)
+    if ".transformer_blocks." in module and module.endswith(SUPPORTED_SUFFIXES):
+        return True
+    if targets == "attention":
+        return False
+    return (".transformer_blocks." in module and module.endswith(FF_SUFFIXES)) or _is_transformer_proj(module)
+
+
+_OPT_IN = " -- pass targets='transformer' to apply it"
 
 
 def _why_unsupported(module):
     if ".ff.net." in module:
-        return "feed-forward target (the GEGLU kernel is fused)"
+        return "feed-forward target (the GEGLU kernel is fused)" + _OPT_IN
     if module.endswith(("proj_in", "proj_out")):
-        return "proj_in / proj_out target"
+        return "proj_in / proj_out target" + _OPT_IN
     if "resnets." in module or module.endswith(("time_emb_proj", "conv1", "conv2", "conv_shortcut", "conv", "conv_in", "conv_out")):
         return "resnet / convolution target"
     return "not an attention projection of a transformer block"
@@ -64,11 +92,14 @@ def _split_key(key):
     return None
 
 
-def parse_lora_state_dict(sd, module_names, ignore_unsupported=False):
+def parse_lora_state_dict(sd, module_names, ignore_unsupported=False, targets="attention"):
     """``sd``: a LoRA checkpoint in any of the three conventions (module docstring); ``module_names``: the model's own module names
     (``down_blocks.0.attentions.0.transformer_blocks.0.attn1.to_q``, ...).  Returns ``{module: (A [r, K], B [N, r], alpha or None)}``
-    with float32 CPU factors, for the supported modules.  Unsupported modules, foreign adapter families, text-encoder keys and ranks
-    above 128 raise ``NotImplementedError`` naming the module; with ``ignore_unsupported`` they are skipped and ONE warning lists them."""
+    with float32 CPU factors, for the modules supported under ``targets`` ("attention": the eight attention projections;
+    "transformer": also ff.net.0.proj, ff.net.2, proj_in and proj_out, whose 1x1-convolution factors [r, in, 1, 1] / [out, r, 1, 1] are
+    squeezed).  Unsupported modules, foreign adapter families, text-encoder keys and ranks above 128 raise ``NotImplementedError``
+    naming the module; with ``ignore_unsupported`` they are skipped and ONE warning lists them."""
+    _check_targets(targets)
     module_names = list(module_names)
     by_flat = {}
     for n in module_names:
@@ -108,12 +139,14 @@ def parse_lora_state_dict(sd, module_names, ignore_unsupported=False):
 
     out = {}
     for name, p in parts.items():
-        if not supported(name):
+        if not supported(name, targets):
             refuse(name, _why_unsupported(name))
             continue
         if _DOWN not in p or _UP not in p:
             raise KeyError(f"LoRA: module {name} has {sorted(p)} -- both the down (lora_A) and the up (lora_B) factor are needed")
         a, b = p[_DOWN], p[_UP]
+        if _is_transformer_proj(name) and a.dim() == 4 and b.dim() == 4 and tuple(a.shape[2:]) == tuple(b.shape[2:]) == (1, 1):
+            a, b = a[:, :, 0, 0], b[:, :, 0, 0]  # kohya / LoCon factors of a 1x1 convolution: the same matrices on tokens
         if a.dim() != 2 or b.dim() != 2:
             refuse(name, f"factors of shape {tuple(a.shape)} / {tuple(b.shape)}: convolution LoRA")
             continue

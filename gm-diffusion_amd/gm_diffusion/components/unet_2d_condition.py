@@ -525,7 +525,7 @@ class UNet2DConditionModel(_HipModule):
 
         def transformer(k, heads, depth):
             """GroupNorm + proj_in / proj_out around ``depth`` BasicTransformerBlocks (1 for SD-1.5; 1 / 2 / 10 per level for SDXL)."""
-            t = dict(norm=self._norm(k + ".norm"), pin=self._lin(k + ".proj_in"), pout=self._lin(k + ".proj_out"), heads=heads, blocks=[])
+            t = dict(norm=self._norm(k + ".norm"), pin=self._lin(k + ".proj_in"), pout=self._lin(k + ".proj_out"), heads=heads, blocks=[], key=k)
             for n_ in range(depth):
                 b = f"{k}.transformer_blocks.{n_}"
                 blk = dict(heads=heads)
@@ -933,18 +933,22 @@ class UNet2DConditionModel(_HipModule):
         """The model's own module names, the table kohya's flattened names are resolved against."""
         return [k[: -len(".weight")] for k in self.expected_keys() if k.endswith(".weight")]
 
-    def load_lora(self, state_dict, ignore_unsupported=False):
+    def load_lora(self, state_dict, ignore_unsupported=False, targets="attention"):
         """Load ONE LoRA adapter (PEFT / diffusers / kohya keys: components/lora.py) for the attention projections of the transformer
-        blocks.  Host work only: the factors go to the device, in the model's dtype and beside the prepared weights, at first use.  No
-        weight buffer changes: every targeted projection is followed by one ``hip_ops.lora_update``."""
+        blocks; ``targets="transformer"`` also takes the feed-forward's ``ff.net.0.proj`` / ``ff.net.2`` and the transformers'
+        ``proj_in`` / ``proj_out``.  Host work only: the factors go to the device, in the model's dtype and beside the prepared weights,
+        at first use.  No weight buffer changes: every targeted projection is followed by one ``hip_ops.lora_update`` (``ff.net.0.proj``:
+        by ``hip_ops.lora_geglu``, the update and the GEGLU in one launch; a block with a feed-forward target leaves ff_geglu_fused)."""
         from . import lora as _lora
 
         if self._lora_raw is not None:
             raise NotImplementedError("load_lora: an adapter is already loaded and several adapters at once are not implemented "
                                       "(unload_lora() first)")
-        parsed = _lora.parse_lora_state_dict(state_dict, self.lora_module_names(), ignore_unsupported=ignore_unsupported)
+        parsed = _lora.parse_lora_state_dict(state_dict, self.lora_module_names(), ignore_unsupported=ignore_unsupported,
+                                             targets=targets)
         if not parsed:
-            raise ValueError("load_lora: the state dict holds no LoRA factors for this UNet's attention projections")
+            raise ValueError("load_lora: the state dict holds no LoRA factors for this UNet's attention projections"
+                             + (", feed-forwards or proj_in / proj_out" if targets == "transformer" else ""))
         shapes = self.expected_keys()
         for name, (a, b, _) in parsed.items():
             n, k = shapes[name + ".weight"][:2]
@@ -1062,8 +1066,16 @@ class UNet2DConditionModel(_HipModule):
             rp = _pad_to(r, mult)
             ap, bp = torch.zeros(rp, a.shape[1]), torch.zeros(b.shape[0], rp)
             ap[:r], bp[:, :r] = a, b
-            blk, proj = name.rsplit(".attn", 1)
-            proj = "attn" + proj
+            if name.endswith(_lora.FF_SUFFIXES):
+                blk, proj = name.split(".ff.net.", 1)
+                proj = "ff.net." + proj
+                if proj == "ff.net.0.proj" and (ops.is_half(self._dtype) or self._split_mode()):
+                    bp = ops.geglu_interleave(bp)  # the row order of the block's ff1 weight (_prepare_encoder): y's columns arrive in it
+            elif name.endswith(_lora.PROJ_SUFFIXES):
+                blk, proj = name.rsplit(".", 1)  # the Transformer2DModel itself
+            else:
+                blk, proj = name.rsplit(".attn", 1)
+                proj = "attn" + proj
             layers.setdefault(blk, {})[proj] = (self._wt(ap), self._wa(bp) if proj.endswith("to_v") else self._wt(bp), i)
             factors.append(_lora.factor(r, alpha))
         factors = torch.tensor(factors, dtype=torch.float32)
@@ -1085,12 +1097,20 @@ class UNet2DConditionModel(_HipModule):
         text conditioning; everything up to the first cross-attention query is computed once, then duplicated (returns 2B rows)."""
         C = x.shape[-1]
         N = H * W
-        h = ops.groupnorm(x, B, self.config.norm_num_groups, t["norm"][0], t["norm"][1], 1e-6, silu=False, split_out=self._sa(t["pin"][0]))
-        h = ops.gemm_nt(h.view(B * N, C), t["pin"][0], bias=t["pin"][1], a_split=ops.is_asplit(h))  # conv1x1 and nn.Linear proj_in are the same GEMM on tokens
+        lt = _lora_layer(self, t)  # the adapter's proj_in / proj_out factors of this transformer, or None
+        g = ops.groupnorm(x, B, self.config.norm_num_groups, t["norm"][0], t["norm"][1], 1e-6, silu=False, split_out=self._sa(t["pin"][0]))
+        h = ops.gemm_nt(g.view(B * N, C), t["pin"][0], bias=t["pin"][1], a_split=ops.is_asplit(g))  # conv1x1 and nn.Linear proj_in are the same GEMM on tokens
+        if lt is not None:  # (under cfg_dup: on the B unique rows)
+            _lora_apply(self, lt, "proj_in", g.view(B * N, C), h, x_split=ops.is_asplit(g))
         for blk in t["blocks"]:
             h, x, B = self._transformer_block(blk, h, x, B, N, C, ehs, cfg_dup, ip)
             cfg_dup = False  # the first cross-attention has duplicated the batch
-        y = ops.gemm_nt(h, t["pout"][0], bias=t["pout"][1], residual=x.view(B * N, C), colstats=self._wants_colstats(H, W))
+        # an adapted proj_out: the epilogue's column statistics would describe the tensor BEFORE the update, so none are produced and
+        # the next GroupNorm (or concat) computes its own (hip_ops._usable_colstats: a tensor without ._colstats)
+        pout_lora = lt is not None and "proj_out" in lt
+        y = ops.gemm_nt(h, t["pout"][0], bias=t["pout"][1], residual=x.view(B * N, C), colstats=self._wants_colstats(H, W) and not pout_lora)
+        if pout_lora:  # after the bias + residual epilogue: the update commutes with both
+            _lora_apply(self, lt, "proj_out", h, y, x_split=ops.is_asplit(h))
         return ops.carry_colstats(y.view(B, N, C), y)
 
     def _transformer_block(self, t, h, x, B, N, C, ehs, cfg_dup, ip=None):
@@ -1136,6 +1156,8 @@ class UNet2DConditionModel(_HipModule):
             _lora_apply(self, lr, "attn2.to_out.0", o.view(B * N, C), h, x_split=ops.is_asplit(o))
         # GEGLU feed-forward
         n3 = ops.layernorm(h, *t["norm3"], split_out=self._sa(t["ff1"][0]))
+        if lr is not None and ("ff.net.0.proj" in lr or "ff.net.2" in lr):  # an adapted feed-forward: two GEMMs, no ff_geglu_fused
+            return self._feed_forward_lora(t, lr, n3, h), x, B
         if t["ff1_fused"] and ops.ff_fused_ok(n3, C):  # the whole feed-forward in one launch: [tokens, 4C] never reaches HBM
             h = ops.ff_geglu_fused(n3, t["ff1"][0], t["ff1"][1], t["ff2"][0], t["ff2"][1], h)
         else:
@@ -1145,6 +1167,27 @@ class UNet2DConditionModel(_HipModule):
                 f = ops.geglu(ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1]))
             h = ops.gemm_nt(f, t["ff2"][0], bias=t["ff2"][1], residual=h)
         return h, x, B
+
+    def _feed_forward_lora(self, t, lr, n3, h):
+        """The feed-forward of a block whose ``ff.net.0.proj`` and / or ``ff.net.2`` is adapted.  The first update has to land in
+        front of the gate, so the first GEMM stores the plain pre-activation [tokens, 8C] and ``hip_ops.lora_geglu`` forms
+        (value + update) * gelu(gate + update) from it in one launch; the second update commutes with ff2's bias and residual, as at
+        to_out.0."""
+        scales = self._lora_w["scales"]
+        e1 = lr.get("ff.net.0.proj")
+        if e1 is not None:
+            y = ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1])
+            if t["ff1_fused"]:  # interleaved ff1 rows (16-bit, float32 split): e1's b rows are permuted alike (_ensure_lora)
+                f = ops.lora_geglu(n3, e1[0], e1[1], y, scales, e1[2], x_split=ops.is_asplit(n3))
+            else:  # float32 exact: [value half | gate half]
+                f = ops.geglu(ops.lora_update(n3, e1[0], e1[1], y, scales, e1[2]))
+        elif t["ff1_fused"]:
+            f = ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1], act=ops.ACT_GEGLU, split_out=self._sa(t["ff2"][0]))
+        else:
+            f = ops.geglu(ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1]))
+        h = ops.gemm_nt(f, t["ff2"][0], bias=t["ff2"][1], residual=h)
+        _lora_apply(self, lr, "ff.net.2", f, h, x_split=ops.is_asplit(f))
+        return h
 
     def set_timestep(self, timestep):
         """Write the timestep into the device scalar read by the embedding kernel (kept outside any

@@ -980,6 +980,67 @@ def lora_update(x, a, b, y, scales, index, transposed=False, tokens=None, fused=
     return scaled_add(y, u, scales, index, out=y)
 
 
+# The update of a feed-forward's first projection with the GEGLU in the same launch (gmd_lora_geglu).  GMD_LORA_GEGLU_FUSED=0 (read
+# once) composes lora_update and geglu_interleaved instead: the A/B switch, and the comparison route of the tests.
+USE_LORA_GEGLU_FUSED = os.environ.get("GMD_LORA_GEGLU_FUSED", "1") != "0"
+GEGLU_GROUP = 16  # rows of one value / gate group of an interleaved ff1 weight (UNet2DConditionModel._prepare_encoder)
+
+
+def geglu_interleave(t):
+    """Rows of ``t`` [2F, ...] from checkpoint order (value half, then gate half) to the order of the interleaved ff1 weight: value
+    rows 0-15, gate rows 0-15, value rows 16-31, ...  F % 16 == 0."""
+    half = t.shape[0] // 2
+    if t.shape[0] != 2 * half or half % GEGLU_GROUP:
+        raise HipExtensionError(f"geglu_interleave: {t.shape[0]} rows are not two halves of a multiple of {GEGLU_GROUP}")
+    rest = t.shape[1:]
+    return torch.stack([t[:half].reshape(half // GEGLU_GROUP, GEGLU_GROUP, *rest), t[half:].reshape(half // GEGLU_GROUP, GEGLU_GROUP, *rest)],
+                       1).reshape(2 * half, *rest)
+
+
+def geglu_interleaved(x):
+    """``geglu`` over the interleaved column layout (``geglu_interleave`` of the projection's rows): [..., 2F] -> [..., F]."""
+    _dev(x)
+    if is_asplit(x):
+        raise HipExtensionError("geglu_interleaved: the input is a pre-split activation (only contractions read that layout)")
+    F2 = x.shape[-1]
+    y = torch.empty(x.shape[:-1] + (F2 // 2,), dtype=x.dtype, device=x.device)
+    check(lib().gmd_geglu_interleaved(_ptr(x), _ptr(y), dtype_code(x.dtype), x.numel() // F2, F2 // 2, _stream()), "gmd_geglu_interleaved")
+    return y
+
+
+def lora_geglu(x, a, b_interleaved, y, scales, index, fused=None, x_split=False):
+    """``geglu(y + scales[index] * (x @ a.T) @ b.T)`` behind the first feed-forward GEMM of an adapted block; returns F [M, 4C].
+    x: [M, C]; a: [Rp, C]; ``b_interleaved``: [8C, Rp] with its rows in the order of the interleaved ff1 weight (``geglu_interleave``);
+    y: [M, 8C], the pre-activation in that column layout (bias included).  16-bit types: ONE launch (gmd_lora_geglu) that reads y once and
+    leaves it unchanged, unless ``fused`` is False (default: USE_LORA_GEGLU_FUSED).  Composed (and float32): ``lora_update`` IN PLACE
+    on y (its own one launch in the 16-bit types), then ``geglu_interleaved``: a read-modify-write of y and one more read of it."""
+    _dev(x, a, b_interleaved, y, scales)
+    index = _ip_scale_arg(scales, index, "lora_geglu")
+    if not (x.dtype == a.dtype == b_interleaved.dtype == y.dtype):
+        raise HipExtensionError(f"lora_geglu: dtype mismatch {x.dtype} / {a.dtype} / {b_interleaved.dtype} / {y.dtype}")
+    if x.dim() != 2 or a.dim() != 2 or b_interleaved.dim() != 2 or y.dim() != 2:
+        raise HipExtensionError("lora_geglu: x, a, b and y must be matrices")
+    M, C = x.shape
+    Rp = a.shape[0]
+    if a.shape[1] != C or tuple(b_interleaved.shape) != (8 * C, Rp) or tuple(y.shape) != (M, 8 * C):
+        raise HipExtensionError(f"lora_geglu: operand shapes inconsistent: x {tuple(x.shape)}, a {tuple(a.shape)}, b {tuple(b_interleaved.shape)}, "
+                                f"y {tuple(y.shape)} (b must be [8C, Rp], y [M, 8C])")
+    if is_asplit(y) or not (x.is_contiguous() and y.is_contiguous()):
+        raise HipExtensionError("lora_geglu: x and y must be contiguous, y no pre-split activation")
+    fused = USE_LORA_GEGLU_FUSED if fused is None else bool(fused)
+    if not (is_half(x.dtype) and fused):
+        return geglu_interleaved(lora_update(x, a, b_interleaved, y, scales, index, x_split=x_split))
+    if Rp > LORA_MAX_RANK:
+        raise HipExtensionError(f"lora_geglu: padded rank {Rp} above {LORA_MAX_RANK}")
+    f = torch.empty((M, 4 * C), dtype=x.dtype, device=x.device)
+    tm, t0 = _timed("lora_geglu")
+    check(lib().gmd_lora_geglu(_ptr(x), _ptr(a), _ptr(b_interleaved), _ptr(y), _ptr(f), dtype_code(x.dtype), M, C, Rp, C, 8 * C, 4 * C,
+                               _ptr(scales), index, _stream()), "gmd_lora_geglu")
+    if tm:
+        tm.end("lora_geglu", 2.0 * M * Rp * 9 * C, (M * 13 * C + Rp * 9 * C) * x.element_size(), t0)
+    return f
+
+
 def softmax_rows(s, cols, scale, out_dtype, ldp=None, causal_nq=0):
     _dev(s)
     _f32(s, "softmax_rows input")

@@ -131,12 +131,15 @@ class _GMPipelineBase(DiffusionPipeline):
         self.unet.disable_freeu()
 
     # ---- LoRA (diffusers' StableDiffusionLoraLoaderMixin, for LOCAL files; one adapter, kept in factors) ---------------------------
-    def load_lora_weights(self, path_or_state_dict, weight_name=None, subfolder=None, ignore_unsupported=False, adapter_name=None, **kwargs):
+    def load_lora_weights(self, path_or_state_dict, weight_name=None, subfolder=None, ignore_unsupported=False, adapter_name=None,
+                          targets="attention", **kwargs):
         """diffusers' ``load_lora_weights`` for LOCAL files: a ``.safetensors`` file, a ``.bin`` / ``.pt`` torch pickle (read with
         ``weights_only=True``), a directory joined with ``subfolder`` and ``weight_name``, or the already-loaded state dict, in the
         PEFT, older diffusers or kohya key convention (components/lora.py).  Nothing is ever downloaded.  The adapter goes into
         ``self.unet`` (the dual pipeline: the SDR UNet; ``pipe.gm_unet.load_lora(...)`` adapts the GM UNet) and is applied at run
-        time by one fused launch per targeted projection; targets that are not built raise unless ``ignore_unsupported``."""
+        time by one fused launch per targeted projection; targets that are not built raise unless ``ignore_unsupported``.
+        ``targets``: "attention" (default: the eight attention projections of each transformer block) or "transformer" (also
+        ff.net.0.proj, ff.net.2, proj_in and proj_out: kohya's default target set)."""
         from ..components import lora as _lora
 
         if adapter_name is not None:
@@ -145,7 +148,7 @@ class _GMPipelineBase(DiffusionPipeline):
         if kwargs:
             raise NotImplementedError(f"load_lora_weights: unsupported arguments {sorted(kwargs)} (local files only)")
         self.unet.load_lora(_lora.load_lora_file(path_or_state_dict, weight_name=weight_name, subfolder=subfolder),
-                            ignore_unsupported=ignore_unsupported)
+                            ignore_unsupported=ignore_unsupported, targets=targets)
 
     def unload_lora_weights(self):
         self.unet.unload_lora()

@@ -620,6 +620,9 @@ int gmd_layernorm(const void* X, void* Y, int dtype, int64_t rows, int C,
                   const float* gamma, const float* beta, float eps, gmd_stream_t stream);
 /* GEGLU: Y[r, f] = X[r, f] * gelu_erf(X[r, F + f]); X [rows, 2F], Y [rows, F] */
 int gmd_geglu(const void* X, void* Y, int dtype, int64_t rows, int F, gmd_stream_t stream);
+/* gmd_geglu over the column layout an interleaved GEGLU projection weight produces (added within ABI v14): value columns of outputs
+ * 16 j .. 16 j + 15 at X columns 32 j .. 32 j + 15, their gates at 32 j + 16 .. 32 j + 31.  F % 16 == 0. */
+int gmd_geglu_interleaved(const void* X, void* Y, int dtype, int64_t rows, int F, gmd_stream_t stream);
 /* sinusoidal timestep embedding (diffusers get_timestep_embedding): out [B, dim] of `dtype`;
  * timestep read from DEVICE memory (t_dev, float32 scalar) so captured graphs can be replayed. */
 int gmd_timestep_embedding(const float* t_dev, void* out, int dtype, int B, int dim,
@@ -711,6 +714,23 @@ int gmd_scaled_add(const void* a, const void* b, void* out, int dtype, int64_t n
 int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N,
                     int64_t ldx, int64_t ldy, int transposed, int batch, int tokens, int64_t strideY,
                     const float* scales, int index, gmd_stream_t stream);
+/* The LoRA update of a feed-forward's first projection (ff.net.0.proj) and its GEGLU as ONE launch (added within ABI v14: one new
+ * entry point, no signature changed; csrc/lora.hip), GMD_BF16 / GMD_F16:
+ *   F[m, f] = round( v * gelu_erf(g) ),   v = float(Y[m, value(f)]) + s U[m, value(f)],   g = float(Y[m, gate(f)]) + s U[m, gate(f)]
+ *   U[m, n] = sum_j T[m, j] * Bw[n, j],   T[m, j] = round( sum_k X[m, k] * Aw[j, k] ),    s = scales[index]
+ * The arithmetic of gmd_lora_update (both sums in float32 on the matrix cores, T rounded ONCE, the scale in float32); v, g, the erf
+ * GELU of gmd_geglu and the product stay in float32, ONE rounding on the store of F.
+ *   X  [M, C], row stride ldx: the feed-forward's input (the LayerNorm output), C % 64 == 0;   Aw [Rp, C];   Bw [8C, Rp]
+ *   Y  [M, 8C], row stride ldy, READ-ONLY: the pre-activation (gmd_gemm_nt with the bias, GMD_ACT_NONE) over the ROW-INTERLEAVED ff1
+ *      weight, so its columns are interleaved in groups of 16 (gmd_geglu_interleaved): value(f) = 32 (f / 16) + f % 16,
+ *      gate(f) = value(f) + 16.  Bw's rows are in that same order (the host permutes them once).
+ *   F  [M, 4C], row stride ldf: every element of rows [0, M) x columns [0, 4C) is written once by one lane, nothing else is
+ *   Rp, scales, index: as gmd_lora_update.  A row's result does not depend on what else is in the launch.  M == 0: GMD_OK.
+ * GMD_ERR_INVALID before a launch: F overlapping X or Y, pointers not 16-byte aligned, leading dimensions not multiples of 8 or too
+ * small, C % 64, Rp % 32, Rp > 128, a NULL scales, X / Y / F beyond 2 GiB.  GMD_F32 and the split dtypes: GMD_ERR_UNSUPPORTED (the
+ * caller composes gmd_gemm_nt twice, gmd_scaled_add and gmd_geglu / gmd_geglu_interleaved). */
+int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                   int64_t ldx, int64_t ldy, int64_t ldf, const float* scales, int index, gmd_stream_t stream);
 /* elementwise cast between F32 and BF16 */
 int gmd_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, gmd_stream_t stream);
 
