@@ -14,29 +14,62 @@ namespace {
 
 constexpr int kThreads = 256;
 
-__global__ __launch_bounds__(kThreads) void latent_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ cur_sample,
-    const float* __restrict__ e1, const float* __restrict__ e2, const float* __restrict__ e3, int B, int64_t chw,
-    int do_cfg, float gs, const float* __restrict__ ratio, float gr, int mode, float sample_coeff,
-    float alpha_delta, float denom, float sqrt_a, float sqrt_1ma, float* __restrict__ eps_out,
-    float* __restrict__ x_prev, float* __restrict__ x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
+// What every step kernel starts from: the UNet's raw output (both halves of the CFG pair when do_cfg: [2B, chw]), the sample, the
+// shape and the guidance scalars.  ratio: cfg_std_ratio_kernel's per-sample std ratio, nullptr = no guidance rescale.  The output
+// pointers and the schedulers' own inputs stay __restrict__ kernel parameters.
+struct StepIn {
+    const float* eps_in;
+    const float* x;
+    int B;
+    int64_t chw;
+    int do_cfg;
+    float gs;
+    const float* ratio;
+    float gr;
+};
+
+// The guided eps of element i: the CFG combine with rescale_noise_cfg, or the plain load.
+__device__ __forceinline__ float guided_eps(const StepIn& in, int64_t i, int64_t n) {
+    float eps;
+    if (in.do_cfg) {
+        const float u = in.eps_in[i], t = in.eps_in[n + i];
+        eps = u + in.gs * (t - u);  // dual.py:1065
+        if (in.ratio) {             // rescale_noise_cfg, dual.py:91-93
+            const float resc = eps * in.ratio[i / in.chw];
+            eps = in.gr * resc + (1.0f - in.gr) * eps;
         }
-        const float xt = x[i];
+    } else {
+        eps = in.eps_in[i];
+    }
+    return eps;
+}
+
+// The pipeline's own x0 (dual.py:1075), from alphas_cumprod[t] of the loop timestep; never clipped.
+__device__ __forceinline__ float pipeline_x0(float xt, float eps, float sqrt_a, float sqrt_1ma) { return (xt - sqrt_1ma * eps) / sqrt_a; }
+
+// The grid-stride loop of every step kernel: update(i, eps, xt) with the guided eps and the sample of element i.  The block size is
+// read by the builtin: blockDim.x is folded into a scalar load of the dispatch's block size only in a kernel's own body, and costs a
+// vector load in front of the loop when read in a device function.
+template <typename Update>
+__device__ __forceinline__ void for_each_guided(const StepIn& in, Update update) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const unsigned threads = __builtin_amdgcn_workgroup_size_x();
+    const int64_t stride = (int64_t)gridDim.x * threads;
+    const int64_t n = (int64_t)in.B * in.chw;
+    for (int64_t i = (int64_t)blockIdx.x * threads + threadIdx.x; i < n; i += stride) {
+        const float eps = guided_eps(in, i, n);
+        const float xt = in.x[i];
+        update(i, eps, xt);
+    }
+}
+
+__global__ __launch_bounds__(kThreads) void latent_step_kernel(
+    StepIn in, const float* __restrict__ cur_sample, const float* __restrict__ e1, const float* __restrict__ e2,
+    const float* __restrict__ e3, int mode, float sample_coeff, float alpha_delta, float denom, float sqrt_a, float sqrt_1ma,
+    float* __restrict__ eps_out, float* __restrict__ x_prev, float* __restrict__ x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
         if (eps_out) eps_out[i] = eps;
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         float m, smp = xt;
         switch (mode) {  // diffusers PNDMScheduler.step_plms
             case 0: m = eps; break;
@@ -46,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void latent_step_kernel(
             default: m = (1.0f / 24.0f) * (55.0f * eps - 59.0f * e1[i] + 37.0f * e2[i] - 9.0f * e3[i]); break;
         }
         x_prev[i] = sample_coeff * smp - alpha_delta * m / denom;  // _get_prev_sample
-    }
+    });
 }
 
 // DPM-Solver++ (dpmsolver++ / midpoint / epsilon) multistep update fused with the CFG combine and both x0 forms, in the
@@ -56,31 +89,16 @@ __global__ __launch_bounds__(kThreads) void latent_step_kernel(
 //   order2 : x_prev = c_x * x - c_m * m0 - c_h * (inv_r0 * (m0 - m1))          multistep_dpm_solver_second_order_update
 // with c_x = sigma_t/sigma_s0, c_m = alpha_t*(exp(-h)-1), c_h = 0.5*c_m computed by the host in float32.
 __global__ __launch_bounds__(kThreads) void dpm_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ m1, int B, int64_t chw, int do_cfg,
-    float gs, const float* __restrict__ ratio, float gr, int order, float sigma_s0, float alpha_s0, float c_x, float c_m, float c_h,
-    float inv_r0, float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out, float* __restrict__ x_prev, float* __restrict__ x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (the pipeline's own x0, from alphas_cumprod[t])
+    StepIn in, const float* __restrict__ m1, int order, float sigma_s0, float alpha_s0, float c_x, float c_m, float c_h, float inv_r0,
+    float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out, float* __restrict__ x_prev, float* __restrict__ x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         const float m0 = (xt - sigma_s0 * eps) / alpha_s0;
         m0_out[i] = m0;
         float r = c_x * xt - c_m * m0;
         if (order == 2) r = r - c_h * (inv_r0 * (m0 - m1[i]));
         x_prev[i] = r;
-    }
+    });
 }
 
 // SDE-DPM-Solver++ ("DPM++ 2M SDE": algorithm_type "sde-dpmsolver++", midpoint or heun, epsilon) multistep update fused with the
@@ -94,33 +112,18 @@ __global__ __launch_bounds__(kThreads) void dpm_step_kernel(
 // (the last step of a final_sigmas_type "zero" schedule): torch adds the zero product there too, and -0.0 + 0.0 is not -0.0.  It
 // is drawn by the HOST scheduler, as for DDPM and DDIM.
 __global__ __launch_bounds__(kThreads) void dpm_sde_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ m1, const float* __restrict__ noise,
-    int B, int64_t chw, int do_cfg, float gs, const float* __restrict__ ratio, float gr, int order, float sigma_s0, float alpha_s0,
-    float c_x, float c_m, float c_h, float inv_r0, float c_n, float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out,
+    StepIn in, const float* __restrict__ m1, const float* __restrict__ noise, int order, float sigma_s0, float alpha_s0, float c_x,
+    float c_m, float c_h, float inv_r0, float c_n, float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out,
     float* __restrict__ x_prev, float* __restrict__ x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (the pipeline's own x0, from alphas_cumprod[t])
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         const float m0 = (xt - sigma_s0 * eps) / alpha_s0;
         m0_out[i] = m0;
         float r = c_x * xt + c_m * m0;
         if (order == 2) r = r + c_h * (inv_r0 * (m0 - m1[i]));
         r = r + c_n * noise[i];
         x_prev[i] = r;
-    }
+    });
 }
 
 // DDPM ancestral step (the scheduler scripts/inference/generate_hdr.py:162 constructs) fused with the CFG combine and the
@@ -131,32 +134,16 @@ __global__ __launch_bounds__(kThreads) void dpm_sde_step_kernel(
 // The noise tensor is drawn by the HOST scheduler with randn_tensor(generator) so that the shared generator of the dual
 // pipeline is consumed in the reference's order (SDR step first, GM step second: stable_diffusion_dual_unet.py:1077, 1093).
 __global__ __launch_bounds__(kThreads) void ddpm_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
-    float gs, const float* __restrict__ ratio, float gr, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range,
-    float x0_coeff, float xt_coeff, float noise_scale, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
-    float* __restrict__ x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (never clipped)
+    StepIn in, const float* __restrict__ noise, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range, float x0_coeff,
+    float xt_coeff, float noise_scale, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev, float* __restrict__ x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         float p0 = (xt - sched_sqrt_1ma * eps) / sched_sqrt_a;
         if (clip) p0 = fminf(fmaxf(p0, -clip_range), clip_range);
         float r = x0_coeff * p0 + xt_coeff * xt;
         if (noise) r = r + noise_scale * noise[i];
         x_prev[i] = r;
-    }
+    });
 }
 
 // DDIM step (the scheduler the pipelines' docstrings name first; `eta` is its dial towards DDPM) fused with the CFG combine
@@ -169,26 +156,11 @@ __global__ __launch_bounds__(kThreads) void ddpm_step_kernel(
 // The add happens whenever a noise tensor is given, also with std == 0 (the last step of a set_alpha_to_one schedule): torch
 // adds the zero product there too, and -0.0 + 0.0 is not -0.0.  The noise is drawn by the HOST scheduler, as for DDPM.
 __global__ __launch_bounds__(kThreads) void ddim_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
-    float gs, const float* __restrict__ ratio, float gr, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range,
-    int use_clipped, float sqrt_a_prev, float dir_coeff, float std, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
-    float* __restrict__ x0, float* __restrict__ pred_x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (never clipped)
+    StepIn in, const float* __restrict__ noise, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range, int use_clipped,
+    float sqrt_a_prev, float dir_coeff, float std, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev, float* __restrict__ x0,
+    float* __restrict__ pred_x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         float p0 = (xt - sched_sqrt_1ma * eps) / sched_sqrt_a;
         if (clip) p0 = fminf(fmaxf(p0, -clip_range), clip_range);
         if (pred_x0) pred_x0[i] = p0;
@@ -196,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void ddim_step_kernel(
         float r = sqrt_a_prev * p0 + dir_coeff * pe;
         if (noise) r = r + std * noise[i];
         x_prev[i] = r;
-    }
+    });
 }
 
 // Latent-consistency (LCM) step -- diffusers' LCMScheduler.step, epsilon prediction -- fused with the CFG combine and the pipeline's
@@ -208,32 +180,17 @@ __global__ __launch_bounds__(kThreads) void ddim_step_kernel(
 // The noise is drawn by the HOST scheduler, as for DDPM and DDIM.  A guidance-embedded UNet runs without the CFG duplicate, but the
 // combine stays available: LCMScheduler also steps a plain UNet.
 __global__ __launch_bounds__(kThreads) void lcm_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
-    float gs, const float* __restrict__ ratio, float gr, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range,
-    float c_skip, float c_out, float sqrt_a_prev, float sqrt_b_prev, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
+    StepIn in, const float* __restrict__ noise, float sched_sqrt_a, float sched_sqrt_1ma, int clip, float clip_range, float c_skip,
+    float c_out, float sqrt_a_prev, float sqrt_b_prev, float sqrt_a, float sqrt_1ma, float* __restrict__ x_prev,
     float* __restrict__ x0, float* __restrict__ denoised) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (never clipped)
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         float p0 = (xt - sched_sqrt_1ma * eps) / sched_sqrt_a;
         if (clip) p0 = p0 < -clip_range ? -clip_range : (p0 > clip_range ? clip_range : p0);  // torch.clamp: a NaN stays a NaN
         const float den = c_out * p0 + c_skip * xt;
         if (denoised) denoised[i] = den;
         x_prev[i] = noise ? sqrt_a_prev * den + sqrt_b_prev * noise[i] : den;
-    }
+    });
 }
 
 // Euler / Euler-ancestral step (diffusers' EulerDiscreteScheduler / EulerAncestralDiscreteScheduler, epsilon prediction, s_churn == 0)
@@ -244,32 +201,16 @@ __global__ __launch_bounds__(kThreads) void lcm_step_kernel(
 //   x_prev = x_prev + noise * sigma_up      ancestral only (noise == nullptr otherwise)
 // The add happens whenever a noise tensor is given, also with sigma_up == 0 (the last step, sigma_to == 0): torch adds the zero
 // product there too, and -0.0 + 0.0 is not -0.0.  The noise is drawn by the HOST scheduler, as for DDPM and DDIM.
-__global__ __launch_bounds__(kThreads) void euler_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ noise, int B, int64_t chw, int do_cfg,
-    float gs, const float* __restrict__ ratio, float gr, float sigma_hat, float dt, float sigma_up, float* __restrict__ x_prev,
-    float* __restrict__ pred_x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
+__global__ __launch_bounds__(kThreads) void euler_step_kernel(StepIn in, const float* __restrict__ noise, float sigma_hat, float dt,
+                                                              float sigma_up, float* __restrict__ x_prev, float* __restrict__ pred_x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
         const float p0 = xt - sigma_hat * eps;
         if (pred_x0) pred_x0[i] = p0;
         const float d = (xt - p0) / sigma_hat;
         float r = xt + d * dt;
         if (noise) r = r + noise[i] * sigma_up;
         x_prev[i] = r;
-    }
+    });
 }
 
 // Linear multistep step (diffusers' LMSDiscreteScheduler, epsilon prediction, orders 1-4) fused with the CFG combine, in the
@@ -282,25 +223,9 @@ __global__ __launch_bounds__(kThreads) void euler_step_kernel(
 // c0..c3 are the integrals of the Lagrange basis polynomials over [sigma, sigma_next], computed by the host in float64 and rounded
 // to float32 once, by the ``float`` argument.  A history pointer beyond order - 1 is never read.
 __global__ __launch_bounds__(kThreads) void lms_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ d1, const float* __restrict__ d2,
-    const float* __restrict__ d3, int B, int64_t chw, int do_cfg, float gs, const float* __restrict__ ratio, float gr, int order,
-    float sigma, float c0, float c1, float c2, float c3, float* __restrict__ d_out, float* __restrict__ x_prev,
-    float* __restrict__ pred_x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
+    StepIn in, const float* __restrict__ d1, const float* __restrict__ d2, const float* __restrict__ d3, int order, float sigma,
+    float c0, float c1, float c2, float c3, float* __restrict__ d_out, float* __restrict__ x_prev, float* __restrict__ pred_x0) {
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
         const float p0 = xt - sigma * eps;
         if (pred_x0) pred_x0[i] = p0;
         const float d = (xt - p0) / sigma;
@@ -310,7 +235,7 @@ __global__ __launch_bounds__(kThreads) void lms_step_kernel(
         if (order >= 3) acc = acc + c2 * d2[i];
         if (order >= 4) acc = acc + c3 * d3[i];
         x_prev[i] = xt + acc;
-    }
+    });
 }
 
 // UniPC predictor-corrector step (Zhao et al. 2023; diffusers' UniPCMultistepScheduler: predict_x0, epsilon prediction, bh1 / bh2,
@@ -326,28 +251,13 @@ __global__ __launch_bounds__(kThreads) void lms_step_kernel(
 // with c_x / p_x = sigma_t/sigma_s, c_m / p_m = alpha_t*phi_1, c_b / p_b = alpha_t*B_h of the two intervals and rho = R^-1 b, all computed
 // by the host in float32.  The kernel divides by r_k, as the host expression does.  A pointer or scalar beyond the orders is never read.
 __global__ __launch_bounds__(kThreads) void unipc_step_kernel(
-    const float* __restrict__ eps_in, const float* __restrict__ x, const float* __restrict__ last, const float* __restrict__ h1,
-    const float* __restrict__ h2, const float* __restrict__ h3, int B, int64_t chw, int do_cfg, float gs, const float* __restrict__ ratio,
-    float gr, int corr_order, int pred_order, float sigma_s, float alpha_s, float c_x, float c_m, float c_b, float c_rho1, float c_rho2,
+    StepIn in, const float* __restrict__ last, const float* __restrict__ h1, const float* __restrict__ h2, const float* __restrict__ h3,
+    int corr_order, int pred_order, float sigma_s, float alpha_s, float c_x, float c_m, float c_b, float c_rho1, float c_rho2,
     float c_rho3, float c_r1, float c_r2, float p_x, float p_m, float p_b, float p_rho1, float p_rho2, float p_r1, float p_r2,
     float sqrt_a, float sqrt_1ma, float* __restrict__ m0_out, float* __restrict__ x_corr, float* __restrict__ x_prev,
     float* __restrict__ x0) {
-    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
-    const int64_t n = (int64_t)B * chw;
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-        float eps;
-        if (do_cfg) {
-            const float u = eps_in[i], t = eps_in[n + i];
-            eps = u + gs * (t - u);  // dual.py:1065
-            if (ratio) {             // rescale_noise_cfg, dual.py:91-93
-                const float resc = eps * ratio[i / chw];
-                eps = gr * resc + (1.0f - gr) * eps;
-            }
-        } else {
-            eps = eps_in[i];
-        }
-        const float xt = x[i];
-        if (x0) x0[i] = (xt - sqrt_1ma * eps) / sqrt_a;  // dual.py:1075 (the pipeline's own x0, from alphas_cumprod[t])
+    for_each_guided(in, [=](int64_t i, float eps, float xt) {
+        if (x0) x0[i] = pipeline_x0(xt, eps, sqrt_a, sqrt_1ma);
         const float m0 = (xt - sigma_s * eps) / alpha_s;
         m0_out[i] = m0;
         float xc = xt;
@@ -371,7 +281,7 @@ __global__ __launch_bounds__(kThreads) void unipc_step_kernel(
             r = r - p_b * acc;
         }
         x_prev[i] = r;
-    }
+    });
 }
 
 // one block per sample: unbiased std over chw of text eps and of the guided eps
@@ -460,6 +370,16 @@ inline int grid_for(int64_t n) {
     return (int)g;
 }
 
+// The launch tail of every gmd_*_step, after its own argument checks: the grid over B * chw elements, the rule that the rescale
+// ratio counts only under CFG, the launch and its check.  `args`: what the kernel takes after its StepIn.
+template <typename Kernel, typename... Args>
+int launch_step(const char* name, Kernel kernel, gmd_stream_t stream, StepIn in, Args... args) {
+    if (!in.do_cfg) in.ratio = nullptr;
+    kernel<<<grid_for((int64_t)in.B * in.chw), kThreads, 0, (hipStream_t)stream>>>(in, args...);
+    GMD_CHECK_LAUNCH(name);
+    return GMD_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -478,11 +398,9 @@ int gmd_latent_step(const float* eps_in, const float* x, const float* cur_sample
     GMD_REQUIRE(mode < 3 || e2, "gmd_latent_step: mode %d needs e2", mode);
     GMD_REQUIRE(mode < 4 || e3, "gmd_latent_step: mode 4 needs e3");
     GMD_REQUIRE(denom != 0.0f && sqrt_alpha != 0.0f, "gmd_latent_step: zero denominator");
-    latent_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, cur_sample, e1, e2, e3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr,
-        guidance_rescale, mode, sample_coeff, alpha_delta, denom, sqrt_alpha, sqrt_one_minus_alpha, eps_out, x_prev, x0);
-    GMD_CHECK_LAUNCH("gmd_latent_step");
-    return GMD_OK;
+    return launch_step("gmd_latent_step", latent_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, cur_sample, e1, e2, e3, mode,
+                       sample_coeff, alpha_delta, denom, sqrt_alpha, sqrt_one_minus_alpha, eps_out, x_prev, x0);
 }
 
 int gmd_dpm_step(const float* eps_in, const float* x, const float* m1, int B, int64_t chw, int do_cfg, float guidance_scale,
@@ -495,11 +413,9 @@ int gmd_dpm_step(const float* eps_in, const float* x, const float* m1, int B, in
     GMD_REQUIRE(order == 1 || order == 2, "gmd_dpm_step: order must be 1 or 2 (got %d)", order);
     GMD_REQUIRE(order == 1 || m1, "gmd_dpm_step: the second-order update needs the previous x0 prediction");
     GMD_REQUIRE(alpha_s0 != 0.0f && (x0 == nullptr || sqrt_alpha != 0.0f), "gmd_dpm_step: zero denominator");
-    dpm_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, m1, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, order, sigma_s0, alpha_s0,
-        c_x, c_m, c_h, inv_r0, sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_prev, x0);
-    GMD_CHECK_LAUNCH("gmd_dpm_step");
-    return GMD_OK;
+    return launch_step("gmd_dpm_step", dpm_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, m1, order, sigma_s0, alpha_s0,
+                       c_x, c_m, c_h, inv_r0, sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_prev, x0);
 }
 
 int gmd_dpm_sde_step(const float* eps_in, const float* x, const float* m1, const float* noise, int B, int64_t chw, int do_cfg,
@@ -515,11 +431,9 @@ int gmd_dpm_sde_step(const float* eps_in, const float* x, const float* m1, const
     GMD_REQUIRE(alpha_s0 != 0.0f && (x0 == nullptr || sqrt_alpha != 0.0f), "gmd_dpm_sde_step: zero denominator");
     // written as !(v >= 0) so that a NaN (the square root of a negative 1 - exp(-2h)) is refused too
     GMD_REQUIRE(c_n >= 0.0f, "gmd_dpm_sde_step: c_n must be >= 0 (got %g)", (double)c_n);
-    dpm_sde_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, m1, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, order, sigma_s0,
-        alpha_s0, c_x, c_m, c_h, inv_r0, c_n, sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_prev, x0);
-    GMD_CHECK_LAUNCH("gmd_dpm_sde_step");
-    return GMD_OK;
+    return launch_step("gmd_dpm_sde_step", dpm_sde_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, m1, noise, order, sigma_s0,
+                       alpha_s0, c_x, c_m, c_h, inv_r0, c_n, sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_prev, x0);
 }
 
 int gmd_ddpm_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
@@ -531,11 +445,10 @@ int gmd_ddpm_step(const float* eps_in, const float* x, const float* noise, int B
     GMD_REQUIRE(eps_in && x && x_prev, "gmd_ddpm_step: null pointer");
     GMD_REQUIRE(sched_sqrt_alpha != 0.0f && (x0 == nullptr || sqrt_alpha != 0.0f), "gmd_ddpm_step: zero denominator");
     GMD_REQUIRE(!clip_sample || clip_range > 0.0f, "gmd_ddpm_step: clip_range must be positive");
-    ddpm_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
-        sched_sqrt_one_minus_alpha, clip_sample, clip_range, x0_coeff, xt_coeff, noise_scale, sqrt_alpha, sqrt_one_minus_alpha, x_prev, x0);
-    GMD_CHECK_LAUNCH("gmd_ddpm_step");
-    return GMD_OK;
+    return launch_step("gmd_ddpm_step", ddpm_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, noise, sched_sqrt_alpha,
+                       sched_sqrt_one_minus_alpha, clip_sample, clip_range, x0_coeff, xt_coeff, noise_scale, sqrt_alpha,
+                       sqrt_one_minus_alpha, x_prev, x0);
 }
 
 int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
@@ -552,12 +465,10 @@ int gmd_ddim_step(const float* eps_in, const float* x, const float* noise, int B
     // written as !(v >= 0) so that a NaN (the square root of a negative 1 - a_prev - std^2) is refused too
     GMD_REQUIRE(dir_coeff >= 0.0f, "gmd_ddim_step: dir_coeff must be >= 0 (got %g)", (double)dir_coeff);
     GMD_REQUIRE(std_dev >= 0.0f, "gmd_ddim_step: std_dev must be >= 0 (got %g)", (double)std_dev);
-    ddim_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
-        sched_sqrt_one_minus_alpha, clip_sample, clip_range, use_clipped, sqrt_alpha_prev, dir_coeff, std_dev, sqrt_alpha,
-        sqrt_one_minus_alpha, x_prev, x0, pred_x0);
-    GMD_CHECK_LAUNCH("gmd_ddim_step");
-    return GMD_OK;
+    return launch_step("gmd_ddim_step", ddim_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, noise, sched_sqrt_alpha,
+                       sched_sqrt_one_minus_alpha, clip_sample, clip_range, use_clipped, sqrt_alpha_prev, dir_coeff, std_dev,
+                       sqrt_alpha, sqrt_one_minus_alpha, x_prev, x0, pred_x0);
 }
 
 int gmd_lcm_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
@@ -575,12 +486,10 @@ int gmd_lcm_step(const float* eps_in, const float* x, const float* noise, int B,
     GMD_REQUIRE(!clip_sample || clip_range > 0.0f, "gmd_lcm_step: clip_range must be positive");
     if (B == 0) return GMD_OK;
     GMD_REQUIRE(eps_in && x && x_prev, "gmd_lcm_step: null pointer");
-    lcm_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sched_sqrt_alpha,
-        sched_sqrt_one_minus_alpha, clip_sample, clip_range, c_skip, c_out, sqrt_alpha_prev, sqrt_beta_prev, sqrt_alpha,
-        sqrt_one_minus_alpha, x_prev, x0, denoised);
-    GMD_CHECK_LAUNCH("gmd_lcm_step");
-    return GMD_OK;
+    return launch_step("gmd_lcm_step", lcm_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, noise, sched_sqrt_alpha,
+                       sched_sqrt_one_minus_alpha, clip_sample, clip_range, c_skip, c_out, sqrt_alpha_prev, sqrt_beta_prev, sqrt_alpha,
+                       sqrt_one_minus_alpha, x_prev, x0, denoised);
 }
 
 int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int B, int64_t chw, int do_cfg, float guidance_scale,
@@ -593,11 +502,9 @@ int gmd_euler_step(const float* eps_in, const float* x, const float* noise, int 
     GMD_REQUIRE(std::isfinite(dt), "gmd_euler_step: dt must be finite (got %g)", (double)dt);
     if (B == 0) return GMD_OK;
     GMD_REQUIRE(eps_in && x && x_prev, "gmd_euler_step: null pointer");
-    euler_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, noise, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, sigma_hat, dt, sigma_up,
-        x_prev, pred_x0);
-    GMD_CHECK_LAUNCH("gmd_euler_step");
-    return GMD_OK;
+    return launch_step("gmd_euler_step", euler_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, noise, sigma_hat, dt, sigma_up,
+                       x_prev, pred_x0);
 }
 
 int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const float* d2, const float* d3, int B, int64_t chw, int do_cfg,
@@ -615,11 +522,9 @@ int gmd_lms_step(const float* eps_in, const float* x, const float* d1, const flo
     GMD_REQUIRE(order < 2 || d1, "gmd_lms_step: order %d needs d1", order);
     GMD_REQUIRE(order < 3 || d2, "gmd_lms_step: order %d needs d2", order);
     GMD_REQUIRE(order < 4 || d3, "gmd_lms_step: order 4 needs d3");
-    lms_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, d1, d2, d3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, order, sigma, c0, c1,
-        c2, c3, d_out, x_prev, pred_x0);
-    GMD_CHECK_LAUNCH("gmd_lms_step");
-    return GMD_OK;
+    return launch_step("gmd_lms_step", lms_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, d1, d2, d3, order, sigma, c0,
+                       c1, c2, c3, d_out, x_prev, pred_x0);
 }
 
 int gmd_unipc_step(const float* eps_in, const float* x, const float* last_sample, const float* h1, const float* h2, const float* h3, int B,
@@ -662,12 +567,10 @@ int gmd_unipc_step(const float* eps_in, const float* x, const float* last_sample
     GMD_REQUIRE((corr_order < 1 && pred_order < 2) || h1, "gmd_unipc_step: corrector order %d / predictor order %d needs h1", corr_order, pred_order);
     GMD_REQUIRE((corr_order < 2 && pred_order < 3) || h2, "gmd_unipc_step: corrector order %d / predictor order %d needs h2", corr_order, pred_order);
     GMD_REQUIRE(corr_order < 3 || h3, "gmd_unipc_step: corrector order 3 needs h3");
-    unipc_step_kernel<<<grid_for((int64_t)B * chw), kThreads, 0, (hipStream_t)stream>>>(
-        eps_in, x, last_sample, h1, h2, h3, B, chw, do_cfg, guidance_scale, do_cfg ? rescale_ratio : nullptr, guidance_rescale, corr_order,
-        pred_order, sigma_s, alpha_s, c_x, c_m, c_b, c_rho1, c_rho2, c_rho3, c_r1, c_r2, p_x, p_m, p_b, p_rho1, p_rho2, p_r1, p_r2,
-        sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_corr, x_prev, x0);
-    GMD_CHECK_LAUNCH("gmd_unipc_step");
-    return GMD_OK;
+    return launch_step("gmd_unipc_step", unipc_step_kernel, stream,
+                       StepIn{eps_in, x, B, chw, do_cfg, guidance_scale, rescale_ratio, guidance_rescale}, last_sample, h1, h2, h3,
+                       corr_order, pred_order, sigma_s, alpha_s, c_x, c_m, c_b, c_rho1, c_rho2, c_rho3, c_r1, c_r2, p_x, p_m, p_b, p_rho1,
+                       p_rho2, p_r1, p_r2, sqrt_alpha, sqrt_one_minus_alpha, m0_out, x_corr, x_prev, x0);
 }
 
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale, float* ratio, gmd_stream_t stream) {

@@ -64,6 +64,52 @@ class _SchedulerBase(ConfigMixin):
     def __len__(self):
         return self.config.num_train_timesteps
 
+    # ---- what the pipelines ask a scheduler (stable_diffusion_gm.py: _use_fused, _predraw_step_noise) ------------------------------
+    has_fused_step = True  # ``fused_step`` runs the CFG combine, x0 and the update as ONE HIP kernel pass on device tensors
+    predraws_noise = False  # True: ``step`` consumes the generator, and the pipelines may draw the noise of every step up front
+
+    def draws_noise(self, timestep, eta=0.0):
+        """True when ``step`` at this timestep consumes the generator.  Here: never, the step is deterministic."""
+        return False
+
+    # ---- what the constructors share -----------------------------------------------------------------------------------------------
+    def _merge_config(self, kwargs):
+        """``_defaults`` overridden by ``kwargs`` as a dict; a key ``_defaults`` does not hold is refused."""
+        cfg = dict(self._defaults)
+        bad = [k for k in kwargs if k not in cfg]
+        if bad:
+            raise TypeError(f"{type(self).__name__}: unexpected arguments {bad}")
+        cfg.update(kwargs)
+        return cfg
+
+    def _register_betas(self, cfg):
+        """``cfg`` becomes ``self.config``; ``betas``, ``alphas`` and ``alphas_cumprod`` are the float32 tables of diffusers."""
+        self.register_to_config(**cfg)
+        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
+        self.alphas = 1.0 - self.betas
+        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+
+    # ---- what the device steps share -----------------------------------------------------------------------------------------------
+    @staticmethod
+    def _on_device(model_output, sample):
+        """True when ``step`` runs as the fused HIP kernel: float32 device tensors."""
+        return model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32
+
+    @staticmethod
+    def _guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale):
+        """The per-sample std ratio of ``rescale_noise_cfg`` (one reduction kernel), or None when the step does not rescale."""
+        return ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+
+    @staticmethod
+    def _step_noise(sample, generator):
+        """One step's noise for a device step, drawn where ``step`` draws it: float32, on the sample's device."""
+        return randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+
+    @staticmethod
+    def _x0_coefs(a):
+        """(sqrt(a), sqrt(1 - a)) of the pipeline's own x0 (dual_unet.py:1072-1075), from ``alphas_cumprod`` of the loop timestep."""
+        return a.sqrt().item(), (1 - a).sqrt().item()
+
 
 class PNDMScheduler(_SchedulerBase):
     _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear",
@@ -71,17 +117,10 @@ class PNDMScheduler(_SchedulerBase):
                      timestep_spacing="leading", steps_offset=0, clip_sample=False)
 
     def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"PNDMScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
+        cfg = self._merge_config(kwargs)
         if cfg["prediction_type"] != "epsilon":
             raise NotImplementedError("only epsilon prediction is implemented")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._register_betas(cfg)
         self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
         self.pndm_order = 4
@@ -196,13 +235,10 @@ class PNDMScheduler(_SchedulerBase):
         mode, t_eff, prev = self._plan(timestep)
         sc, ad, dn = self._coefs(t_eff, prev)
         a = self.alphas_cumprod[int(timestep)]  # dual_unet.py:1072 uses the loop timestep
-        ratio = None
-        if do_cfg and guidance_rescale > 0.0:
-            ratio = ops.cfg_std_ratio(eps_in, guidance_scale)
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         hist = [e for e in reversed(self.ets[-3:])] if self.counter != 1 else [self.ets[-1]]
         nh = {0: 0, 1: 1, 2: 1, 3: 2, 4: 3}[mode]
-        eps, prev_sample, x0 = ops.latent_step(eps_in, sample.contiguous(), mode,
-                                               (sc.item(), ad.item(), dn.item(), a.sqrt().item(), (1 - a).sqrt().item()),
+        eps, prev_sample, x0 = ops.latent_step(eps_in, sample.contiguous(), mode, (sc.item(), ad.item(), dn.item(), *self._x0_coefs(a)),
                                                do_cfg, guidance_scale, cur_sample=self.cur_sample, hist=hist[:nh], ratio=ratio,
                                                guidance_rescale=guidance_rescale, want_x0=want_x0)
         self._commit(mode, eps, sample)
@@ -216,19 +252,12 @@ class DDPMScheduler(_SchedulerBase):
                      timestep_spacing="leading", steps_offset=0, rescale_betas_zero_snr=False)
 
     def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"DDPMScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
+        cfg = self._merge_config(kwargs)
         if cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["rescale_betas_zero_snr"]:
             raise NotImplementedError("only epsilon prediction without thresholding / zero-SNR rescale is implemented")
         if cfg["variance_type"] not in ("fixed_small", "fixed_small_log", "fixed_large"):
             raise NotImplementedError(cfg["variance_type"])
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._register_betas(cfg)
         self.one = torch.tensor(1.0)
         self.init_noise_sigma = 1.0
         self.custom_timesteps = False
@@ -279,7 +308,9 @@ class DDPMScheduler(_SchedulerBase):
             variance = cur_b
         return variance
 
-    def draws_noise(self, timestep):
+    predraws_noise = True
+
+    def draws_noise(self, timestep, eta=0.0):
         """True when ``step`` at this timestep consumes the generator (every step but t == 0)."""
         return int(timestep) > 0
 
@@ -300,13 +331,12 @@ class DDPMScheduler(_SchedulerBase):
         scale = 0.0  # (noise: the caller's pre-drawn tensor, or drawn below)
         if t > 0:
             if noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order: see fused_step)
-                noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+                noise = self._step_noise(sample, generator)
             v = self._get_variance(t)
             scale = (v if self.config.variance_type == "fixed_small_log" else v ** 0.5).item()
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         return ops.ddpm_step(eps_in.contiguous(), sample.contiguous(),
-                             ((a_t ** 0.5).item(), (b_t ** 0.5).item(), x0_coeff.item(), xt_coeff.item(), scale,
-                              a_t.sqrt().item(), (1 - a_t).sqrt().item()),
+                             ((a_t ** 0.5).item(), (b_t ** 0.5).item(), x0_coeff.item(), xt_coeff.item(), scale, *self._x0_coefs(a_t)),
                              do_cfg, guidance_scale, noise=noise, ratio=ratio, guidance_rescale=guidance_rescale,
                              clip_range=self.config.clip_sample_range if self.config.clip_sample else None, want_x0=want_x0)
 
@@ -318,7 +348,7 @@ class DDPMScheduler(_SchedulerBase):
         return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0, generator, noise)
 
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, noise)
             return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
         return self._host_step(model_output, timestep, sample, generator, return_dict)
@@ -360,17 +390,10 @@ class DDIMScheduler(_SchedulerBase):
                      timestep_spacing="leading", rescale_betas_zero_snr=False)
 
     def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"DDIMScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
+        cfg = self._merge_config(kwargs)
         if cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["rescale_betas_zero_snr"]:
             raise NotImplementedError("only epsilon prediction without thresholding / zero-SNR rescale is implemented")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._register_betas(cfg)
         self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
         self.num_inference_steps = None
@@ -396,6 +419,8 @@ class DDIMScheduler(_SchedulerBase):
         else:
             raise ValueError(f"{c.timestep_spacing} is not supported. Please make sure to choose one of 'leading' or 'trailing'.")
         self.timesteps = torch.from_numpy(timesteps).to(device)
+
+    predraws_noise = True
 
     def draws_noise(self, timestep, eta=0.0):
         """True when ``step`` at this timestep consumes the generator: iff eta > 0, at EVERY step (the last one included, where
@@ -426,12 +451,12 @@ class DDIMScheduler(_SchedulerBase):
         sa, s1, sp, dc, sd, a_t = self._coefs(timestep, eta)
         if eta > 0:
             if noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order: see fused_step)
-                noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
+                noise = self._step_noise(sample, generator)
         else:
             noise = None
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         return ops.ddim_step(eps_in.contiguous(), sample.contiguous(),
-                             (sa.item(), s1.item(), sp.item(), dc.item(), sd.item(), a_t.sqrt().item(), (1 - a_t).sqrt().item()),
+                             (sa.item(), s1.item(), sp.item(), dc.item(), sd.item(), *self._x0_coefs(a_t)),
                              do_cfg, guidance_scale, noise=noise, ratio=ratio, guidance_rescale=guidance_rescale,
                              clip_range=self.config.clip_sample_range if self.config.clip_sample else None,
                              use_clipped=use_clipped_model_output, want_x0=want_x0, want_pred_x0=want_pred_x0)
@@ -454,7 +479,7 @@ class DDIMScheduler(_SchedulerBase):
                              " `variance_noise` stays `None`.")
         if variance_noise is None:
             variance_noise = noise
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, _, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, variance_noise, eta,
                                             use_clipped_model_output, want_pred_x0=True)
             return (prev, p0) if not return_dict else DDIMSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
@@ -500,17 +525,10 @@ class LCMScheduler(_SchedulerBase):
                      timestep_spacing="leading", timestep_scaling=10.0, rescale_betas_zero_snr=False)
 
     def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"LCMScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
+        cfg = self._merge_config(kwargs)
         if cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["rescale_betas_zero_snr"]:
             raise NotImplementedError("only epsilon prediction without thresholding / zero-SNR rescale is implemented")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._register_betas(cfg)
         self.final_alpha_cumprod = torch.tensor(1.0) if cfg["set_alpha_to_one"] else self.alphas_cumprod[0]
         self.init_noise_sigma = 1.0
         self.num_inference_steps = None
@@ -582,7 +600,9 @@ class LCMScheduler(_SchedulerBase):
             raise ValueError(f"timestep {t} is not in the schedule {self._ts_host}")
         self._step_index = idx[1] if len(idx) > 1 else idx[0]
 
-    def draws_noise(self, timestep):
+    predraws_noise = True
+
+    def draws_noise(self, timestep, eta=0.0):
         """True when ``step`` at this timestep consumes the generator: every step but the schedule's last."""
         return int(timestep) != self._ts_host[-1]
 
@@ -619,10 +639,10 @@ class LCMScheduler(_SchedulerBase):
         if last:
             noise = None
         elif noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order: see fused_step)
-            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+            noise = self._step_noise(sample, generator)
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         out = ops.lcm_step(eps_in.contiguous(), sample.contiguous(),
-                           (sa.item(), s1.item(), cs.item(), co.item(), sp.item(), bp.item(), a_t.sqrt().item(), (1 - a_t).sqrt().item()),
+                           (sa.item(), s1.item(), cs.item(), co.item(), sp.item(), bp.item(), *self._x0_coefs(a_t)),
                            do_cfg, guidance_scale, noise=noise, ratio=ratio, guidance_rescale=guidance_rescale,
                            clip_range=self.config.clip_sample_range if self.config.clip_sample else None,
                            want_x0=want_x0, want_denoised=want_denoised)
@@ -638,7 +658,7 @@ class LCMScheduler(_SchedulerBase):
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
         """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor: what ``generator`` would have given
         at this step, so it may come together with the generator, which it leaves untouched."""
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, _, den = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, noise, want_denoised=True)
             return (prev, den) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=den)
         return self._host_step(model_output, timestep, sample, generator, return_dict, noise)
@@ -662,44 +682,12 @@ class LCMScheduler(_SchedulerBase):
         return (prev, denoised) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=denoised)
 
 
-class DPMSolverMultistepScheduler(_SchedulerBase):
-    """DPM-Solver++ multistep scheduler: the one the reference swaps in for the dual-UNet text->HDR runs
-    (``DPMSolverMultistepScheduler.from_config(pipeline.scheduler.config)``,
-    scripts/inference/experiments/formal_improved.py:195; scripts/stage2/experiments/scheduler_tuning.py:190-201).
-    Implements diffusers' ``dpmsolver++`` and ``sde-dpmsolver++`` ("DPM++ 2M SDE") algorithms with the ``midpoint`` and ``heun``
-    solver types on the epsilon-prediction path, ``solver_order`` 1-2, ``lower_order_final``, ``euler_at_final`` and
-    ``final_sigmas_type`` zero / sigma_min; Karras / exponential / beta sigma schedules, the non-``++`` algorithms, order 3 and
-    thresholding raise NotImplementedError.  The reference's runs pass ``eta=0.7  # Controls stochasticity`` to the pipeline
-    (formal_improved.py:267), which this solver has no argument for: ``algorithm_type="sde-dpmsolver++"`` is the stochastic
-    sampling that comment intends.  The SDE algorithm draws noise once per step, the last included, after the x0 prediction.
-    A host-side state machine over the scheduler protocol: ``step`` / ``fused_step`` run as ONE HIP kernel (gmd_dpm_step, or
-    gmd_dpm_sde_step for the SDE algorithm) for float32 device tensors, as the same torch expressions on the host otherwise
-    (SURVEY.md §8f-2)."""
+class _MultistepSolverBase(_SchedulerBase):
+    """What ``DPMSolverMultistepScheduler`` and ``UniPCMultistepScheduler`` share (same config keys, same arithmetic): the state a
+    constructor leaves, the timestep / sigma tables of ``set_timesteps``, the step-index rule and sigma -> (alpha_t, sigma_t)."""
 
-    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
-                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
-                     sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
-                     euler_at_final=False, use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False,
-                     final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0, clip_sample=False)
-
-    def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"DPMSolverMultistepScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
-        if (cfg["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++") or cfg["solver_type"] not in ("midpoint", "heun")
-                or cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["use_karras_sigmas"]
-                or cfg["use_exponential_sigmas"] or cfg["use_beta_sigmas"] or cfg["solver_order"] not in (1, 2)):
-            raise NotImplementedError("only dpmsolver++ / sde-dpmsolver++, midpoint / heun, epsilon, solver_order <= 2, plain sigmas"
-                                      " are implemented")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.alpha_t = torch.sqrt(self.alphas_cumprod)
-        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
-        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+    def _init_solver(self, cfg):
+        self._register_betas(cfg)
         self.sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
         self.init_noise_sigma = 1.0
         self.num_inference_steps = None
@@ -755,6 +743,39 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         else:
             self._step_index = idx[1] if len(idx) > 1 else idx[0]
 
+
+class DPMSolverMultistepScheduler(_MultistepSolverBase):
+    """DPM-Solver++ multistep scheduler: the one the reference swaps in for the dual-UNet text->HDR runs
+    (``DPMSolverMultistepScheduler.from_config(pipeline.scheduler.config)``,
+    scripts/inference/experiments/formal_improved.py:195; scripts/stage2/experiments/scheduler_tuning.py:190-201).
+    Implements diffusers' ``dpmsolver++`` and ``sde-dpmsolver++`` ("DPM++ 2M SDE") algorithms with the ``midpoint`` and ``heun``
+    solver types on the epsilon-prediction path, ``solver_order`` 1-2, ``lower_order_final``, ``euler_at_final`` and
+    ``final_sigmas_type`` zero / sigma_min; Karras / exponential / beta sigma schedules, the non-``++`` algorithms, order 3 and
+    thresholding raise NotImplementedError.  The reference's runs pass ``eta=0.7  # Controls stochasticity`` to the pipeline
+    (formal_improved.py:267), which this solver has no argument for: ``algorithm_type="sde-dpmsolver++"`` is the stochastic
+    sampling that comment intends.  The SDE algorithm draws noise once per step, the last included, after the x0 prediction.
+    A host-side state machine over the scheduler protocol: ``step`` / ``fused_step`` run as ONE HIP kernel (gmd_dpm_step, or
+    gmd_dpm_sde_step for the SDE algorithm) for float32 device tensors, as the same torch expressions on the host otherwise
+    (SURVEY.md §8f-2)."""
+
+    _defaults = dict(num_train_timesteps=1000, beta_start=0.0001, beta_end=0.02, beta_schedule="linear", trained_betas=None,
+                     solver_order=2, prediction_type="epsilon", thresholding=False, dynamic_thresholding_ratio=0.995,
+                     sample_max_value=1.0, algorithm_type="dpmsolver++", solver_type="midpoint", lower_order_final=True,
+                     euler_at_final=False, use_karras_sigmas=False, use_exponential_sigmas=False, use_beta_sigmas=False,
+                     final_sigmas_type="zero", timestep_spacing="linspace", steps_offset=0, clip_sample=False)
+
+    def __init__(self, **kwargs):
+        cfg = self._merge_config(kwargs)
+        if (cfg["algorithm_type"] not in ("dpmsolver++", "sde-dpmsolver++") or cfg["solver_type"] not in ("midpoint", "heun")
+                or cfg["prediction_type"] != "epsilon" or cfg["thresholding"] or cfg["use_karras_sigmas"]
+                or cfg["use_exponential_sigmas"] or cfg["use_beta_sigmas"] or cfg["solver_order"] not in (1, 2)):
+            raise NotImplementedError("only dpmsolver++ / sde-dpmsolver++, midpoint / heun, epsilon, solver_order <= 2, plain sigmas"
+                                      " are implemented")
+        self._init_solver(cfg)
+        self.alpha_t = torch.sqrt(self.alphas_cumprod)
+        self.sigma_t = torch.sqrt(1 - self.alphas_cumprod)
+        self.lambda_t = torch.log(self.alpha_t) - torch.log(self.sigma_t)
+
     def _plan_step(self, timestep):
         """Host side of one step: (order, float32 0-dim coefficient tensors) computed exactly as diffusers computes them."""
         if self.num_inference_steps is None:
@@ -788,10 +809,14 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
             self.lower_order_nums += 1
         self._step_index += 1
 
-    def draws_noise(self, timestep):
+    def draws_noise(self, timestep, eta=0.0):
         """True when ``step`` at this timestep consumes the generator: iff the algorithm is an SDE one, then at EVERY step (the last
         included, where the noise coefficient may be 0)."""
         return self.config.algorithm_type == "sde-dpmsolver++"
+
+    @property
+    def predraws_noise(self):
+        return self.draws_noise(None)
 
     def _update_coefs(self, first, alpha_t, sigma_t, sigma_s0, h):
         """(c_x, c_m, c_h, c_n) of ``x_prev = c_x x + c_m D0 + c_h D1 + c_n noise`` (SDE) or ``c_x x - c_m D0 - c_h D1`` (deterministic;
@@ -821,18 +846,18 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         inv_r0 = (1.0 / r0) if r0 is not None else torch.tensor(0.0)
         a = self.alphas_cumprod[int(timestep)]  # the pipeline's own x0 (dual_unet.py:1072) uses the loop timestep
         if c_n is not None and noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order)
-            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+            noise = self._step_noise(sample, generator)
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         m1 = None if first else self.model_outputs[-1]
         if c_n is None:
             m0, prev, x0 = ops.dpm_step(eps_in.contiguous(), sample.contiguous(), 1 if first else 2,
                                         (sigma_s0.item(), alpha_s0.item(), c_x.item(), c_m.item(), c_h.item(), inv_r0.item(),
-                                         a.sqrt().item(), (1 - a).sqrt().item()),
+                                         *self._x0_coefs(a)),
                                         do_cfg, guidance_scale, m1=m1, ratio=ratio, guidance_rescale=guidance_rescale, want_x0=want_x0)
         else:
             m0, prev, x0 = ops.dpm_sde_step(eps_in.contiguous(), sample.contiguous(), 1 if first else 2,
                                             (sigma_s0.item(), alpha_s0.item(), c_x.item(), c_m.item(), c_h.item(), inv_r0.item(),
-                                             c_n.item(), a.sqrt().item(), (1 - a).sqrt().item()),
+                                             c_n.item(), *self._x0_coefs(a)),
                                             do_cfg, guidance_scale, noise.contiguous(), m1=m1, ratio=ratio,
                                             guidance_rescale=guidance_rescale, want_x0=want_x0)
         self._advance(m0)
@@ -849,7 +874,7 @@ class DPMSolverMultistepScheduler(_SchedulerBase):
         algorithm, and the generator is then not touched; the deterministic algorithm ignores all three."""
         if variance_noise is None:
             variance_noise = noise
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False, generator, variance_noise)
             return (prev,) if not return_dict else SchedulerOutput(prev_sample=prev)
         prev = self._host_step(model_output, timestep, sample, generator, variance_noise)
@@ -909,12 +934,7 @@ class _SigmaSchedulerBase(_SchedulerBase):
     _name = "_SigmaSchedulerBase"
 
     def _init_sigma_space(self, kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"{self._name}: unexpected arguments {bad}")
-        cfg.update(kwargs)
-        self.register_to_config(**cfg)
+        cfg = self._merge_config(kwargs)
         if cfg["prediction_type"] != "epsilon":
             raise NotImplementedError(f"{self._name}: only prediction_type 'epsilon' is implemented (got {cfg['prediction_type']!r})")
         if cfg.get("interpolation_type", "linear") != "linear":
@@ -927,9 +947,7 @@ class _SigmaSchedulerBase(_SchedulerBase):
             raise NotImplementedError(f"{self._name}: exponential and beta sigmas are not implemented (plain and Karras sigmas are)")
         if cfg.get("rescale_betas_zero_snr", False):
             raise NotImplementedError(f"{self._name}: rescale_betas_zero_snr is not implemented")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
+        self._register_betas(cfg)
         sigmas = (((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5).flip(0)
         ts = np.linspace(0, cfg["num_train_timesteps"] - 1, cfg["num_train_timesteps"], dtype=float)[::-1].copy()
         self.timesteps = torch.from_numpy(ts).to(dtype=torch.float32)
@@ -1077,10 +1095,6 @@ class EulerDiscreteScheduler(_SigmaSchedulerBase):
         if self.config.sigma_min is not None or self.config.sigma_max is not None:
             raise NotImplementedError("EulerDiscreteScheduler: sigma_min / sigma_max overrides of the Karras range are not implemented")
 
-    def draws_noise(self, timestep):
-        """False: without churn the Euler step never consumes the generator."""
-        return False
-
     def _coefs(self, timestep, s_churn):
         if s_churn > 0:
             raise NotImplementedError("EulerDiscreteScheduler: s_churn > 0 (stochastic churn) is not implemented")
@@ -1092,7 +1106,7 @@ class EulerDiscreteScheduler(_SigmaSchedulerBase):
         """One HIP kernel pass (gmd_euler_step): CFG combine (+rescale), x0 prediction and the Euler update.
         Returns (prev_sample, pred_original_sample | None)."""
         sigma_hat, dt = self._coefs(timestep, s_churn)
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         out = ops.euler_step(eps_in.contiguous(), sample.contiguous(), (sigma_hat.item(), dt.item(), 0.0), do_cfg, guidance_scale,
                              ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
         self._step_index += 1
@@ -1107,7 +1121,7 @@ class EulerDiscreteScheduler(_SigmaSchedulerBase):
     def step(self, model_output, timestep, sample, s_churn=0.0, s_tmin=0.0, s_tmax=float("inf"), s_noise=1.0, generator=None,
              return_dict=True, noise=None):
         """diffusers' signature; ``noise`` (not in diffusers) is what the pipelines pass to every stochastic scheduler: unused here."""
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, s_churn)
             return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
         return self._host_step(model_output, timestep, sample, s_churn, return_dict)
@@ -1137,7 +1151,9 @@ class EulerAncestralDiscreteScheduler(_SigmaSchedulerBase):
     def __init__(self, **kwargs):
         self._init_sigma_space(kwargs)
 
-    def draws_noise(self, timestep):
+    predraws_noise = True
+
+    def draws_noise(self, timestep, eta=0.0):
         """True: ``step`` consumes the generator at every step, the last included."""
         return True
 
@@ -1155,8 +1171,8 @@ class EulerAncestralDiscreteScheduler(_SigmaSchedulerBase):
         two schedulers of the dual pipeline is consumed in call order (SDR first, GM second)."""
         sigma, dt, sigma_up = self._coefs(timestep)
         if noise is None:  # (the pipelines pre-draw a CPU generator's noise for all steps, in call order)
-            noise = randn_tensor(sample.shape, generator=generator, device=sample.device, dtype=torch.float32)
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+            noise = self._step_noise(sample, generator)
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         out = ops.euler_step(eps_in.contiguous(), sample.contiguous(), (sigma.item(), dt.item(), sigma_up.item()), do_cfg, guidance_scale,
                              noise=noise.contiguous(), ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
         self._step_index += 1
@@ -1170,7 +1186,7 @@ class EulerAncestralDiscreteScheduler(_SigmaSchedulerBase):
     def step(self, model_output, timestep, sample, generator=None, return_dict=True, noise=None):
         """diffusers' signature; ``noise`` (not in diffusers) is the pipelines' pre-drawn tensor: what ``generator`` would have
         given at this step, so it may come together with the generator, which is then not touched."""
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, generator, noise)
             return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
         return self._host_step(model_output, timestep, sample, generator, return_dict, noise)
@@ -1224,10 +1240,6 @@ class LMSDiscreteScheduler(_SigmaSchedulerBase):
         self._sig64 = self.sigmas.numpy().astype(np.float64).tolist()
         self.derivatives = []
 
-    def draws_noise(self, timestep):
-        """False: the step is deterministic and never consumes a generator."""
-        return False
-
     def get_lms_coefficient(self, order, t, current_order):
         """The integral over [sigma_t, sigma_{t+1}] of the Lagrange basis polynomial that is 1 at sigma_{t - current_order} and 0 at
         the other nodes sigma_{t-k}, k < order, as a Python float (float64).  The integrand stays in product form: expanded into
@@ -1272,7 +1284,7 @@ class LMSDiscreteScheduler(_SigmaSchedulerBase):
         derivative kept as history is the kernel's own output, never ``eps_in`` (which may be the static output buffer of a captured
         graph that the next replay overwrites).  Returns (prev_sample, pred_original_sample | None)."""
         sigma, k, coeffs = self._plan(timestep, order)
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         hist = list(reversed(self.derivatives))[:k - 1]
         d, prev, p0 = ops.lms_step(eps_in.contiguous(), sample.contiguous(), k, [sigma.item()] + coeffs + [0.0] * (4 - k), do_cfg,
                                    guidance_scale, hist=hist, ratio=ratio, guidance_rescale=guidance_rescale, want_pred_x0=want_x0)
@@ -1293,7 +1305,7 @@ class LMSDiscreteScheduler(_SigmaSchedulerBase):
         bad = [k for k in ignored if k not in ("generator", "noise")]
         if bad:
             raise TypeError(f"{self._name}.step: unexpected arguments {bad}")
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, p0 = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, True, order)
             return (prev, p0) if not return_dict else EulerSchedulerOutput(prev_sample=prev, pred_original_sample=p0)
         return self._host_step(model_output, timestep, sample, order, return_dict)
@@ -1324,14 +1336,14 @@ class _UniPCPlan:
         return [self.sigma_s.item(), self.alpha_s.item()] + corr + pred
 
 
-class UniPCMultistepScheduler(_SchedulerBase):
+class UniPCMultistepScheduler(_MultistepSolverBase):
     """UniPC (Zhao et al. 2023, diffusers' ``UniPCMultistepScheduler``): a multistep predictor of order 1-3 whose previous update is
     repaired by a corrector that re-uses the model output of the CURRENT step, so the correction costs no UNet evaluation.  The sampler
     for 8-20 steps with an ordinary checkpoint.  Implemented: ``predict_x0`` with epsilon prediction, ``solver_type`` bh1 / bh2,
     ``solver_order`` 1-3, ``lower_order_final``, ``disable_corrector``, ``final_sigmas_type`` zero / sigma_min, the three spacings;
     Karras / exponential / beta / flow sigmas, ``predict_x0=False``, ``solver_p``, thresholding, zero-SNR betas and other prediction
     types raise NotImplementedError.  Variance-preserving: ``init_noise_sigma`` is 1 and ``scale_model_input`` the identity; tables and
-    the step-index rule are ``DPMSolverMultistepScheduler``'s.  A host-side state machine: ``step`` / ``fused_step`` run as ONE HIP
+    the step-index rule are those of ``DPMSolverMultistepScheduler`` (``_MultistepSolverBase``).  A host-side state machine: ``step`` / ``fused_step`` run as ONE HIP
     kernel (gmd_unipc_step: x0, corrector and predictor) for float32 device tensors, as the torch expressions of ``_host_step``
     otherwise.
 
@@ -1349,15 +1361,10 @@ class UniPCMultistepScheduler(_SchedulerBase):
     MAX_ORDER = 3  # gmd_unipc_step reads at most three earlier x0 predictions
 
     def __init__(self, **kwargs):
-        cfg = dict(self._defaults)
-        bad = [k for k in kwargs if k not in cfg]
-        if bad:
-            raise TypeError(f"UniPCMultistepScheduler: unexpected arguments {bad}")
-        cfg.update(kwargs)
+        cfg = self._merge_config(kwargs)
         cfg["disable_corrector"] = list(cfg["disable_corrector"] or [])
         if cfg["solver_type"] in ("midpoint", "heun", "logrho"):  # another solver's config (from_config): diffusers falls to bh2 too
             cfg["solver_type"] = "bh2"
-        self.register_to_config(**cfg)
         for key in ("use_karras_sigmas", "use_exponential_sigmas", "use_beta_sigmas", "use_flow_sigmas", "thresholding",
                     "rescale_betas_zero_snr"):
             if cfg[key]:
@@ -1372,39 +1379,18 @@ class UniPCMultistepScheduler(_SchedulerBase):
             raise NotImplementedError(f"UniPCMultistepScheduler: solver_type={cfg['solver_type']!r} is not implemented (bh1, bh2)")
         if cfg["solver_order"] not in (1, 2, 3):
             raise NotImplementedError(f"UniPCMultistepScheduler: solver_order={cfg['solver_order']!r} is not implemented (1..{self.MAX_ORDER})")
-        self.betas = _betas(cfg["beta_schedule"], cfg["beta_start"], cfg["beta_end"], cfg["num_train_timesteps"], cfg["trained_betas"])
-        self.alphas = 1.0 - self.betas
-        self.alphas_cumprod = torch.cumprod(self.alphas, dim=0)
-        self.sigmas = ((1 - self.alphas_cumprod) / self.alphas_cumprod) ** 0.5
-        self.init_noise_sigma = 1.0
-        self.num_inference_steps = None
-        self.timesteps = torch.from_numpy(np.linspace(0, cfg["num_train_timesteps"] - 1, cfg["num_train_timesteps"], dtype=np.float32)[::-1].copy())
-        self.model_outputs = [None] * cfg["solver_order"]
-        self.lower_order_nums = 0
+        self._init_solver(cfg)
         self.last_sample = None
         self.this_order = None
-        self._step_index = None
-
-    @property
-    def step_index(self):
-        return self._step_index
 
     def set_timesteps(self, num_inference_steps=None, device=None):
-        """The timestep and sigma tables of ``DPMSolverMultistepScheduler.set_timesteps`` (same config keys, same arithmetic), which
-        also clears ``model_outputs``, ``lower_order_nums`` and the step index."""
-        DPMSolverMultistepScheduler.set_timesteps(self, num_inference_steps, device)
+        super().set_timesteps(num_inference_steps, device)
         self.last_sample = None
         self.this_order = None
-
-    _init_step_index = DPMSolverMultistepScheduler._init_step_index
-
-    def draws_noise(self, timestep):
-        """False: the step is deterministic and never consumes a generator."""
-        return False
 
     def _lambda(self, k):
         """(alpha, sigma, lambda) of sigma-table entry k as float32 0-d tensors."""
-        alpha, sigma = DPMSolverMultistepScheduler._sigma_to_alpha_sigma_t(self.sigmas[k])
+        alpha, sigma = self._sigma_to_alpha_sigma_t(self.sigmas[k])
         return alpha, sigma, torch.log(alpha) - torch.log(sigma)
 
     def _rb(self, h, rks):
@@ -1475,10 +1461,10 @@ class UniPCMultistepScheduler(_SchedulerBase):
         static output buffer of a captured graph) nor the caller's ``sample``.  Returns (prev_sample, x0 | None)."""
         pl = self._plan_step(timestep)
         a = self.alphas_cumprod[int(timestep)]  # the pipeline's own x0 (dual_unet.py:1072) uses the loop timestep
-        ratio = ops.cfg_std_ratio(eps_in, guidance_scale) if (do_cfg and guidance_rescale > 0.0) else None
+        ratio = self._guidance_ratio(eps_in, do_cfg, guidance_scale, guidance_rescale)
         hist = list(reversed(self.model_outputs))[:max(pl.p, pl.q - 1)]
         m0, corrected, prev, x0 = ops.unipc_step(eps_in.contiguous(), sample.contiguous(), pl.p, pl.q,
-                                                 pl.floats() + [a.sqrt().item(), (1 - a).sqrt().item()], do_cfg, guidance_scale,
+                                                 pl.floats() + [*self._x0_coefs(a)], do_cfg, guidance_scale,
                                                  last_sample=self.last_sample if pl.p else None, hist=hist, ratio=ratio,
                                                  guidance_rescale=guidance_rescale, want_x0=want_x0)
         self._advance(m0, corrected, pl)
@@ -1490,7 +1476,7 @@ class UniPCMultistepScheduler(_SchedulerBase):
         return self._device_step(eps_in, timestep, sample, do_cfg, guidance_scale, guidance_rescale, want_x0)
 
     def step(self, model_output, timestep, sample, return_dict=True):
-        if model_output.is_cuda and model_output.dtype == torch.float32 and sample.dtype == torch.float32:
+        if self._on_device(model_output, sample):
             prev, _ = self._device_step(model_output, timestep, sample, False, 1.0, 0.0, False)
         else:
             prev = self._host_step(model_output, timestep, sample)

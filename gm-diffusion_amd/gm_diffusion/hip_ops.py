@@ -1538,60 +1538,55 @@ def cfg_std_ratio(eps_pair, guidance_scale):
     return ratio
 
 
+def _shape_differs(x, *tensors):
+    return any(t is not None and t.shape != x.shape for t in tensors)
+
+
+def _fused_step(entry, eps_in, x, inputs, guide, scalars, n_out, want=(), hist=None, refuse=()):
+    """What the fused latent steps share: every gmd_*_step takes (eps_in, x, <inputs>, B, chw, <guide>, <scalars>, <outputs>, stream).
+    ``inputs``: the entry point's further input tensors in its order (None = a null pointer); ``hist``: a history that follows them,
+    newest first, of which three entries are passed (None-padded; None: the entry point takes no history); ``guide`` = (do_cfg, guidance_scale, ratio, guidance_rescale);
+    ``refuse``: (condition, message) pairs of the caller's own refusals, looked at in order after the device and float32 checks.
+    Returns ``n_out`` tensors like ``x`` and then one per ``want`` flag (None where it is false), allocated HERE at every call:
+    what a scheduler keeps as history is never the static buffer of a captured graph.  ``entry`` is looked up on ``lib()`` now."""
+    do_cfg, guidance_scale, ratio, guidance_rescale = guide
+    _dev(eps_in, x, ratio, *inputs, *(hist or ()))
+    for t in (eps_in, x, *inputs, *(hist or ())):
+        _f32(t, "latent tensors")
+    for bad, message in refuse:
+        if bad:
+            raise HipExtensionError(message)
+    if hist is not None:
+        inputs = (*inputs, *hist[:3], *[None] * (3 - len(hist[:3])))
+    outs = [torch.empty_like(x) for _ in range(n_out)] + [torch.empty_like(x) if w else None for w in want]
+    check(getattr(lib(), entry)(_ptr(eps_in), _ptr(x), *(_ptr(t) for t in inputs), x.shape[0], x.shape[1:].numel(), int(do_cfg),
+                                float(guidance_scale), _ptr(ratio), float(guidance_rescale), *scalars, *(_ptr(t) for t in outs),
+                                _stream()), entry)
+    return tuple(outs)
+
+
 def latent_step(eps_in, x, mode, coefs, do_cfg, guidance_scale, cur_sample=None, hist=(), ratio=None,
                 guidance_rescale=0.0, want_x0=False):
     """Fused CFG + x0 + PLMS update.  coefs = (sample_coeff, alpha_delta, denom, sqrt_alpha, sqrt_one_minus_alpha).
     Returns (eps, x_prev, x0|None)."""
-    _dev(eps_in, x, cur_sample, ratio, *hist)
-    for t in (eps_in, x, cur_sample, *hist):
-        _f32(t, "latent tensors")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    eps_out = torch.empty_like(x)
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    h = list(hist) + [None] * (3 - len(hist))
     sc, ad, dn, sa, s1 = (float(c) for c in coefs)
-    check(lib().gmd_latent_step(_ptr(eps_in), _ptr(x), _ptr(cur_sample), _ptr(h[0]), _ptr(h[1]), _ptr(h[2]), B, chw,
-                                int(do_cfg), float(guidance_scale), _ptr(ratio), float(guidance_rescale), mode,
-                                sc, ad, dn, sa, s1, _ptr(eps_out), _ptr(x_prev), _ptr(x0), _stream()), "gmd_latent_step")
-    return eps_out, x_prev, x0
+    return _fused_step("gmd_latent_step", eps_in, x, (cur_sample,), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (mode, sc, ad, dn, sa, s1), 2, (want_x0,), hist=hist)
 
 
 def dpm_step(eps_in, x, order, coefs, do_cfg, guidance_scale, m1=None, ratio=None, guidance_rescale=0.0, want_x0=False):
     """Fused CFG + x0 + DPM-Solver++ (orders 1-2) update.  coefs = (sigma_s0, alpha_s0, c_x, c_m, c_h, inv_r0, sqrt_alpha,
     sqrt_one_minus_alpha).  Returns (m0, x_prev, x0|None)."""
-    _dev(eps_in, x, m1, ratio)
-    for t in (eps_in, x, m1):
-        _f32(t, "latent tensors")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    m0 = torch.empty_like(x)
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    c = [float(v) for v in coefs]
-    check(lib().gmd_dpm_step(_ptr(eps_in), _ptr(x), _ptr(m1), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                             float(guidance_rescale), int(order), *c, _ptr(m0), _ptr(x_prev), _ptr(x0), _stream()), "gmd_dpm_step")
-    return m0, x_prev, x0
+    return _fused_step("gmd_dpm_step", eps_in, x, (m1,), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (int(order), *(float(v) for v in coefs)), 2, (want_x0,))
 
 
 def dpm_sde_step(eps_in, x, order, coefs, do_cfg, guidance_scale, noise, m1=None, ratio=None, guidance_rescale=0.0, want_x0=False):
     """Fused CFG + x0 + SDE-DPM-Solver++ (orders 1-2) update.  coefs = (sigma_s0, alpha_s0, c_x, c_m, c_h, inv_r0, c_n, sqrt_alpha,
     sqrt_one_minus_alpha); ``noise`` is required and added at every step (also with c_n == 0).  Returns (m0, x_prev, x0|None)."""
-    _dev(eps_in, x, m1, noise, ratio)
-    for t in (eps_in, x, m1, noise):
-        _f32(t, "latent tensors")
-    if noise is None or noise.shape != x.shape:
-        raise HipExtensionError("dpm_sde_step: noise must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    m0 = torch.empty_like(x)
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    c = [float(v) for v in coefs]
-    check(lib().gmd_dpm_sde_step(_ptr(eps_in), _ptr(x), _ptr(m1), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                                 float(guidance_rescale), int(order), *c, _ptr(m0), _ptr(x_prev), _ptr(x0), _stream()), "gmd_dpm_sde_step")
-    return m0, x_prev, x0
+    return _fused_step("gmd_dpm_sde_step", eps_in, x, (m1, noise), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (int(order), *(float(v) for v in coefs)), 2, (want_x0,),
+                       refuse=[(noise is None or _shape_differs(x, noise), "dpm_sde_step: noise must have the sample's shape")])
 
 
 def ddpm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, clip_range=None,
@@ -1599,20 +1594,10 @@ def ddpm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, 
     """Fused CFG + x0 + DDPM ancestral update.  coefs = (sched_sqrt_alpha, sched_sqrt_one_minus_alpha, x0_coeff, xt_coeff,
     noise_scale, sqrt_alpha, sqrt_one_minus_alpha); ``noise`` is None at the last step (t == 0); ``clip_range`` None = no
     clip_sample.  Returns (x_prev, x0|None)."""
-    _dev(eps_in, x, noise, ratio)
-    for t in (eps_in, x, noise):
-        _f32(t, "latent tensors")
-    if noise is not None and noise.shape != x.shape:
-        raise HipExtensionError("ddpm_step: noise must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
     sa, s1, c0, ct, ns, pa, p1 = (float(v) for v in coefs)
-    check(lib().gmd_ddpm_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                              float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), c0, ct, ns, pa, p1,
-                              _ptr(x_prev), _ptr(x0), _stream()), "gmd_ddpm_step")
-    return x_prev, x0
+    return _fused_step("gmd_ddpm_step", eps_in, x, (noise,), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (sa, s1, int(clip_range is not None), float(clip_range or 0.0), c0, ct, ns, pa, p1), 1, (want_x0,),
+                       refuse=[(_shape_differs(x, noise), "ddpm_step: noise must have the sample's shape")])
 
 
 def ddim_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, clip_range=None,
@@ -1621,21 +1606,10 @@ def ddim_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, 
     sqrt_alpha, sqrt_one_minus_alpha); ``noise`` is None when eta == 0 and is added whenever given (also with std_dev == 0);
     ``clip_range`` None = no clip_sample; ``use_clipped`` = use_clipped_model_output.  Returns (x_prev, x0|None, pred_x0|None):
     x0 is the pipeline's never-clipped prediction, pred_x0 diffusers' (clipped) pred_original_sample."""
-    _dev(eps_in, x, noise, ratio)
-    for t in (eps_in, x, noise):
-        _f32(t, "latent tensors")
-    if noise is not None and noise.shape != x.shape:
-        raise HipExtensionError("ddim_step: noise must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
     sa, s1, sp, dc, sd, pa, p1 = (float(v) for v in coefs)
-    check(lib().gmd_ddim_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                              float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), int(bool(use_clipped)),
-                              sp, dc, sd, pa, p1, _ptr(x_prev), _ptr(x0), _ptr(pred_x0), _stream()), "gmd_ddim_step")
-    return x_prev, x0, pred_x0
+    return _fused_step("gmd_ddim_step", eps_in, x, (noise,), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (sa, s1, int(clip_range is not None), float(clip_range or 0.0), int(bool(use_clipped)), sp, dc, sd, pa, p1),
+                       1, (want_x0, want_pred_x0), refuse=[(_shape_differs(x, noise), "ddim_step: noise must have the sample's shape")])
 
 
 def lcm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, clip_range=None,
@@ -1645,39 +1619,18 @@ def lcm_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, g
     denoised sample itself; ``clip_range`` None = no clip_sample.  Returns (x_prev, x0|None, denoised|None): x0 is the pipeline's
     never-clipped prediction, denoised = c_out * p0 + c_skip * x.  The outputs are allocated here, so nothing the scheduler keeps
     is ever the static buffer of a captured graph."""
-    _dev(eps_in, x, noise, ratio)
-    for t in (eps_in, x, noise):
-        _f32(t, "latent tensors")
-    if noise is not None and noise.shape != x.shape:
-        raise HipExtensionError("lcm_step: noise must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    x_prev = torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    denoised = torch.empty_like(x) if want_denoised else None
     sa, s1, cs, co, sp, bp, pa, p1 = (float(v) for v in coefs)
-    check(lib().gmd_lcm_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                             float(guidance_rescale), sa, s1, int(clip_range is not None), float(clip_range or 0.0), cs, co, sp, bp,
-                             pa, p1, _ptr(x_prev), _ptr(x0), _ptr(denoised), _stream()), "gmd_lcm_step")
-    return x_prev, x0, denoised
+    return _fused_step("gmd_lcm_step", eps_in, x, (noise,), (do_cfg, guidance_scale, ratio, guidance_rescale),
+                       (sa, s1, int(clip_range is not None), float(clip_range or 0.0), cs, co, sp, bp, pa, p1), 1, (want_x0, want_denoised),
+                       refuse=[(_shape_differs(x, noise), "lcm_step: noise must have the sample's shape")])
 
 
 def euler_step(eps_in, x, coefs, do_cfg, guidance_scale, noise=None, ratio=None, guidance_rescale=0.0, want_pred_x0=False):
     """Fused CFG + Euler / Euler-ancestral update.  coefs = (sigma_hat, dt, sigma_up); ``noise`` is None for the deterministic
     scheduler and is added whenever given (also with sigma_up == 0).  Returns (x_prev, pred_x0|None): pred_x0 = x - sigma_hat eps."""
-    _dev(eps_in, x, noise, ratio)
-    for t in (eps_in, x, noise):
-        _f32(t, "latent tensors")
-    if noise is not None and noise.shape != x.shape:
-        raise HipExtensionError("euler_step: noise must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    x_prev = torch.empty_like(x)
-    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
     sh, dt, su = (float(v) for v in coefs)
-    check(lib().gmd_euler_step(_ptr(eps_in), _ptr(x), _ptr(noise), B, chw, int(do_cfg), float(guidance_scale), _ptr(ratio),
-                               float(guidance_rescale), sh, dt, su, _ptr(x_prev), _ptr(pred_x0), _stream()), "gmd_euler_step")
-    return x_prev, pred_x0
+    return _fused_step("gmd_euler_step", eps_in, x, (noise,), (do_cfg, guidance_scale, ratio, guidance_rescale), (sh, dt, su), 1,
+                       (want_pred_x0,), refuse=[(_shape_differs(x, noise), "euler_step: noise must have the sample's shape")])
 
 
 def lms_step(eps_in, x, order, coefs, do_cfg, guidance_scale, hist=(), ratio=None, guidance_rescale=0.0, want_pred_x0=False):
@@ -1685,25 +1638,12 @@ def lms_step(eps_in, x, order, coefs, do_cfg, guidance_scale, hist=(), ratio=Non
     previous steps, newest first, of which the first order - 1 are read.  Returns (d, x_prev, pred_x0|None): d = the step's
     derivative, pred_x0 = x - sigma eps.  The three outputs are allocated here, so the derivative the caller keeps as history is
     never the static buffer of a captured graph."""
-    _dev(eps_in, x, ratio, *hist)
-    for t in (eps_in, x, *hist):
-        _f32(t, "latent tensors")
     order = int(order)
-    if len(hist) < order - 1:
-        raise HipExtensionError(f"lms_step: order {order} needs {order - 1} earlier derivatives (got {len(hist)})")
-    if any(h.shape != x.shape for h in hist):
-        raise HipExtensionError("lms_step: a history tensor must have the sample's shape")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    d = torch.empty_like(x)
-    x_prev = torch.empty_like(x)
-    pred_x0 = torch.empty_like(x) if want_pred_x0 else None
-    h = list(hist[:3]) + [None] * (3 - len(hist[:3]))
     sg, c0, c1, c2, c3 = (float(v) for v in coefs)
-    check(lib().gmd_lms_step(_ptr(eps_in), _ptr(x), _ptr(h[0]), _ptr(h[1]), _ptr(h[2]), B, chw, int(do_cfg), float(guidance_scale),
-                             _ptr(ratio), float(guidance_rescale), order, sg, c0, c1, c2, c3, _ptr(d), _ptr(x_prev), _ptr(pred_x0),
-                             _stream()), "gmd_lms_step")
-    return d, x_prev, pred_x0
+    return _fused_step("gmd_lms_step", eps_in, x, (), (do_cfg, guidance_scale, ratio, guidance_rescale), (order, sg, c0, c1, c2, c3), 2,
+                       (want_pred_x0,), hist=hist,
+                       refuse=[(len(hist) < order - 1, f"lms_step: order {order} needs {order - 1} earlier derivatives (got {len(hist)})"),
+                               (_shape_differs(x, *hist), "lms_step: a history tensor must have the sample's shape")])
 
 
 def unipc_step(eps_in, x, corr_order, pred_order, coefs, do_cfg, guidance_scale, last_sample=None, hist=(), ratio=None, guidance_rescale=0.0,
@@ -1713,29 +1653,17 @@ def unipc_step(eps_in, x, corr_order, pred_order, coefs, do_cfg, guidance_scale,
     sqrt_one_minus_alpha).  ``hist``: the x0 predictions of the previous steps, newest first (at most three are passed on);
     ``last_sample``: the corrected sample of the previous step.  Returns (m0, x_corr, x_prev, x0|None), all allocated here, so what the
     caller keeps as history is never the static buffer of a captured graph nor the caller's own sample."""
-    _dev(eps_in, x, last_sample, ratio, *hist)
-    for t in (eps_in, x, last_sample, *hist):
-        _f32(t, "latent tensors")
     p, q = int(corr_order), int(pred_order)
     need = max(p, q - 1)
-    if len(hist) < need:
-        raise HipExtensionError(f"unipc_step: corrector order {p} / predictor order {q} needs {need} earlier x0 predictions (got {len(hist)})")
-    if p >= 1 and last_sample is None:
-        raise HipExtensionError(f"unipc_step: corrector order {p} needs last_sample")
-    if any(h.shape != x.shape for h in (*hist, *(() if last_sample is None else (last_sample,)))):
-        raise HipExtensionError("unipc_step: history tensors and last_sample must have the sample's shape")
     c = [float(v) for v in coefs]
-    if len(c) != 19:
-        raise HipExtensionError(f"unipc_step: 19 coefficients expected (got {len(c)})")
-    B = x.shape[0]
-    chw = x.shape[1:].numel()
-    m0, x_corr, x_prev = torch.empty_like(x), torch.empty_like(x), torch.empty_like(x)
-    x0 = torch.empty_like(x) if want_x0 else None
-    h = list(hist[:3]) + [None] * (3 - len(hist[:3]))
-    check(lib().gmd_unipc_step(_ptr(eps_in), _ptr(x), _ptr(last_sample), _ptr(h[0]), _ptr(h[1]), _ptr(h[2]), B, chw, int(do_cfg),
-                               float(guidance_scale), _ptr(ratio), float(guidance_rescale), p, q, *c, _ptr(m0), _ptr(x_corr), _ptr(x_prev),
-                               _ptr(x0), _stream()), "gmd_unipc_step")
-    return m0, x_corr, x_prev, x0
+    return _fused_step("gmd_unipc_step", eps_in, x, (last_sample,), (do_cfg, guidance_scale, ratio, guidance_rescale), (p, q, *c), 3,
+                       (want_x0,), hist=hist,
+                       refuse=[(len(hist) < need, f"unipc_step: corrector order {p} / predictor order {q} needs {need} earlier x0"
+                                                  f" predictions (got {len(hist)})"),
+                               (p >= 1 and last_sample is None, f"unipc_step: corrector order {p} needs last_sample"),
+                               (_shape_differs(x, last_sample, *hist),
+                                "unipc_step: history tensors and last_sample must have the sample's shape"),
+                               (len(c) != 19, f"unipc_step: 19 coefficients expected (got {len(c)})")])
 
 
 # ----------------------------------------------------------------------------------------------

@@ -54,7 +54,6 @@ import torch
 
 from ..components.configuration import FrozenDict
 from ..components.image_processor import StableDiffusionPipelineOutput, VaeImageProcessor, randn_tensor
-from ..components.schedulers import PNDMScheduler
 from .pipeline_utils import DiffusionPipeline
 
 logger = logging.getLogger(__name__)
@@ -460,13 +459,8 @@ class _GMPipelineBase(DiffusionPipeline):
     def _use_fused(self, latents, unet, scheduler):
         from ..components.unet_2d_condition import UNet2DConditionModel
 
-        from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                                             EulerDiscreteScheduler, LCMScheduler, LMSDiscreteScheduler, UniPCMultistepScheduler)
-
-        return (latents.is_cuda and isinstance(scheduler, (PNDMScheduler, DPMSolverMultistepScheduler, DDPMScheduler, DDIMScheduler, LCMScheduler,
-                                                            EulerDiscreteScheduler, EulerAncestralDiscreteScheduler, LMSDiscreteScheduler,
-                                                            UniPCMultistepScheduler))
-                and isinstance(unet, UNet2DConditionModel))
+        # the scheduler says itself whether it has a fused device step (components.schedulers: every class there does)
+        return latents.is_cuda and getattr(scheduler, "has_fused_step", False) and isinstance(unet, UNet2DConditionModel)
 
     @staticmethod
     def _pack_div(scheduler, timestep):
@@ -494,18 +488,12 @@ class _GMPipelineBase(DiffusionPipeline):
         at every step but the last, as DDPM does.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
-        from ..components.schedulers import (DDIMScheduler, DDPMScheduler, DPMSolverMultistepScheduler, EulerAncestralDiscreteScheduler,
-                                             LCMScheduler)
-
-        takes_part = lambda s_: (isinstance(s_, (DDPMScheduler, DDIMScheduler, EulerAncestralDiscreteScheduler, LCMScheduler))
-                                 or (isinstance(s_, DPMSolverMultistepScheduler) and s_.draws_noise(None)))
-        if generator is None or not all(takes_part(s_) for s_ in schedulers):
+        if generator is None or not all(getattr(s_, "predraws_noise", False) for s_ in schedulers):
             return None
         gens = generator if isinstance(generator, list) else [generator]
         if any(g_.device.type != "cpu" for g_ in gens):
             return None
-        draws = lambda s_, t: s_.draws_noise(t, eta) if isinstance(s_, DDIMScheduler) else s_.draws_noise(t)
-        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers) if draws(s_, t)]
+        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers) if s_.draws_noise(t, eta)]
         if not slots:
             return None
         nbytes = 4 * len(slots)

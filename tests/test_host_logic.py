@@ -509,6 +509,51 @@ def test_predrawn_scheduler_noise_is_capped_and_ordered():
         P.PREDRAW_NOISE_BYTES = old
 
 
+def _scheduler_protocol_cases():
+    """(id, class name, constructor kwargs, eta, takes part in the pre-draw, the pre-draw has something to draw)."""
+    yes = [("ddpm", "DDPMScheduler", {}, 0.0, True), ("ddim-eta0.5", "DDIMScheduler", {}, 0.5, True),
+           ("euler-ancestral", "EulerAncestralDiscreteScheduler", {}, 0.0, True), ("lcm", "LCMScheduler", {}, 0.0, True),
+           ("dpm-sde", "DPMSolverMultistepScheduler", dict(algorithm_type="sde-dpmsolver++"), 0.0, True)]
+    no = [("pndm", "PNDMScheduler", dict(skip_prk_steps=True), 0.0), ("dpm", "DPMSolverMultistepScheduler", dict(algorithm_type="dpmsolver++"), 0.0),
+          ("euler", "EulerDiscreteScheduler", {}, 0.0), ("lms", "LMSDiscreteScheduler", {}, 0.0), ("unipc", "UniPCMultistepScheduler", {}, 0.0)]
+    return ([pytest.param(n, kw, eta, True, drawn, id=i) for i, n, kw, eta, drawn in yes]
+            + [pytest.param("DDIMScheduler", {}, 0.0, True, False, id="ddim-eta0")]  # takes part, but eta 0 draws nothing
+            + [pytest.param(n, kw, eta, False, False, id=i) for i, n, kw, eta in no])
+
+
+@pytest.mark.parametrize("name,kwargs,eta,takes_part,drawn", _scheduler_protocol_cases())
+def test_pipelines_ask_the_scheduler_not_a_class_list(name, kwargs, eta, takes_part, drawn):
+    """What ``_use_fused`` and ``_predraw_step_noise`` used to read off ``isinstance`` lists, every scheduler now says itself: all nine
+    classes have a fused step; DDPM, DDIM, Euler ancestral, LCM and SDE-DPM++ take part in the pre-draw, the deterministic ones
+    (PNDM, DPM++, Euler, LMS, UniPC) do not; and every one answers ``draws_noise(timestep, eta)`` (DDIM at eta 0: nothing to draw)."""
+    from gm_diffusion import components
+    from gm_diffusion.components import UNet2DConditionModel
+
+    class FakeLatents:
+        is_cuda = True
+
+    s = getattr(components, name)(**kwargs)
+    pipe = StableDiffusionGMPipeline.__new__(StableDiffusionGMPipeline)
+    unet = UNet2DConditionModel.__new__(UNet2DConditionModel)
+    assert pipe._use_fused(FakeLatents(), unet, s) is True
+    assert not pipe._use_fused(FakeLatents(), unet, object()) and not pipe._use_fused(FakeLatents(), object(), s)
+    assert s.predraws_noise is takes_part
+    s.set_timesteps(3)
+    ts = s.timesteps.tolist()
+    g = torch.Generator().manual_seed(3)
+    pre = StableDiffusionGMPipeline._predraw_step_noise([s], ts, (1, 4, 2, 2), g, "cpu", eta=eta)
+    assert (pre is not None) == drawn
+    if drawn:
+        assert [n is not None for n in pre[0]] == [bool(s.draws_noise(t, eta)) for t in ts]
+    else:
+        assert not any(s.draws_noise(t, eta) for t in ts)
+        assert torch.equal(g.get_state(), torch.Generator().manual_seed(3).get_state())  # the generator was not touched
+    # the mixed case: one scheduler of a pair does not take part, and nothing is pre-drawn
+    other = components.UniPCMultistepScheduler()
+    other.set_timesteps(3)
+    assert StableDiffusionGMPipeline._predraw_step_noise([s, other], ts, (1, 4, 2, 2), torch.Generator().manual_seed(3), "cpu", eta=eta) is None
+
+
 def test_float32_contraction_mode_selection():
     """Which dtype code a contraction gets (hip_ops._contract_code): float32 tensors go to the matrix cores as three float16
     products (GMD_F32S, or GMD_F32SW for a pre-split weight) in mode 'split' when K is a multiple of 32, to the exact FMA
