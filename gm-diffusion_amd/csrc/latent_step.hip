@@ -1,5 +1,5 @@
 // Latent-side kernels of the denoising loop: CFG combine + x0 prediction + PNDM/PLMS update in one
-// pass (and its siblings for DPM-Solver++, DDPM, DDIM, LCM, Euler, LMS and UniPC), the guidance-rescale std reduction, and the UNet input pack / output unpack (8-channel
+// pass (and its siblings for DPM-Solver++, DDPM, DDIM, LCM, Euler, LMS and UniPC), the guidance-rescale std reduction, the img2img start / inpaint blend, and the UNet input pack / output unpack (8-channel
 // concat + CFG duplicate + NCHW<->channels-last + cast + channel padding).
 //
 // Built with -ffp-contract=off: float32 operations are issued in the same order as the torch
@@ -7,6 +7,7 @@
 #include "gmd_common.h"
 
 #include <cmath>
+#include <cstdint>
 
 #pragma clang fp contract(off)
 
@@ -363,6 +364,34 @@ __global__ __launch_bounds__(kThreads) void unpack_kernel(const T* __restrict__ 
     }
 }
 
+// img2img start / inpaint blend of one step, in the float32 operation order of the torch expressions (no FMA contraction):
+//   keep   = noise ? ca * z0 + cb * noise : z0           scheduler.add_noise(z0, noise, t_next); z0 itself at the last step
+//   x_prev = mask ? (1 - m) * keep + m * x_prev : keep   diffusers' inpaint rule; with a null mask x_prev is written, never read
+//   x0     = (1 - m) * z0 + m * x0                       the clean picture where it is kept (x0 may be nullptr)
+// mask: [mask_rows, hw], one row for every sample or one per sample, broadcast over the C channels.  No shortcut at m == 0 or 1:
+// 0 * inf is NaN here as in torch.  x_prev and x0 are read and written by the same thread only.
+__global__ __launch_bounds__(kThreads) void inpaint_blend_kernel(float* __restrict__ x_prev, float* __restrict__ x0,
+                                                                 const float* __restrict__ mask, const float* __restrict__ z0,
+                                                                 const float* __restrict__ noise, int64_t n, int64_t chw, int64_t hw,
+                                                                 int per_sample, float ca, float cb) {
+    GMD_WG_TRACE_SCOPE(WGK_LATENT_STEP);
+    const unsigned threads = __builtin_amdgcn_workgroup_size_x();
+    const int64_t stride = (int64_t)gridDim.x * threads;
+    for (int64_t i = (int64_t)blockIdx.x * threads + threadIdx.x; i < n; i += stride) {
+        const float z = z0[i];
+        const float keep = noise ? ca * z + cb * noise[i] : z;
+        if (!mask) {
+            x_prev[i] = keep;
+            continue;
+        }
+        const int64_t p = i % hw;
+        const float m = mask[(per_sample ? (i / chw) * hw : 0) + p];
+        const float om = 1.0f - m;
+        if (x_prev) x_prev[i] = om * keep + m * x_prev[i];
+        if (x0) x0[i] = om * z + m * x0[i];
+    }
+}
+
 inline int grid_for(int64_t n) {
     int64_t g = (n + kThreads - 1) / kThreads;
     if (g > 2048) g = 2048;
@@ -579,6 +608,22 @@ int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_sc
     GMD_REQUIRE(eps_in && ratio, "gmd_cfg_std_ratio: null pointer");
     cfg_std_ratio_kernel<<<B, kThreads, 0, (hipStream_t)stream>>>(eps_in, B, chw, guidance_scale, ratio);
     GMD_CHECK_LAUNCH("gmd_cfg_std_ratio");
+    return GMD_OK;
+}
+
+int gmd_inpaint_blend(float* x_prev, float* x0, const float* mask, const float* z0, const float* noise, int B, int C, int64_t hw,
+                      int mask_rows, float ca, float cb, gmd_stream_t stream) {
+    GMD_REQUIRE(B >= 0 && C >= 0 && hw >= 0, "gmd_inpaint_blend: negative shape");
+    GMD_REQUIRE(hw == 0 || (int64_t)B * C <= INT64_MAX / hw, "gmd_inpaint_blend: B * C * hw overflows");
+    const int64_t n = (int64_t)B * C * hw;
+    if (n == 0) return GMD_OK;
+    GMD_REQUIRE(z0, "gmd_inpaint_blend: null z0");
+    GMD_REQUIRE(x_prev || x0, "gmd_inpaint_blend: both outputs are null");
+    GMD_REQUIRE(mask || !x0, "gmd_inpaint_blend: x0 is blended by the mask, which is null");
+    GMD_REQUIRE(mask_rows == 1 || mask_rows == B, "gmd_inpaint_blend: mask_rows %d is neither 1 nor B = %d", mask_rows, B);
+    inpaint_blend_kernel<<<grid_for(n), kThreads, 0, (hipStream_t)stream>>>(x_prev, x0, mask, z0, noise, n, (int64_t)C * hw, hw,
+                                                                            mask_rows != 1, ca, cb);
+    GMD_CHECK_LAUNCH("gmd_inpaint_blend");
     return GMD_OK;
 }
 

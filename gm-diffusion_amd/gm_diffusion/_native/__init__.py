@@ -47,6 +47,7 @@ SIGNATURES = {
     "gmd_lms_step": [P, P, P, P, P, I, L, I, F, P, F, I, F, F, F, F, F, P, P, P, P],
     "gmd_unipc_step": [P, P, P, P, P, P, I, L, I, F, P, F, I, I] + [F] * 19 + [P, P, P, P, P],
     "gmd_cfg_std_ratio": [P, I, L, F, P, P],
+    "gmd_inpaint_blend": [P, P, P, P, P, I, I, L, I, F, F, P],
     "gmd_pack_unet_input": [P, I, P, I, I, L, I, P, I, I, P],
     "gmd_pack_unet_input_scaled": [P, I, F, P, I, F, I, L, I, P, I, I, P],
     "gmd_unpack_nchw": [P, I, L, I, I, L, P, P],

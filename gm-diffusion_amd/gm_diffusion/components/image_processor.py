@@ -90,6 +90,46 @@ class VaeImageProcessor:
             return [Image.fromarray(im.squeeze(), mode="L") for im in images]
         return [Image.fromarray(im) for im in images]
 
+    @staticmethod
+    def normalize(images):
+        """diffusers' ``2.0 * images - 1.0``: [0, 1] -> [-1, 1]."""
+        return 2.0 * images - 1.0
+
+    def preprocess(self, image, height=None, width=None):
+        """The img2img input as the VAE takes it: float32 NCHW in [-1, 1].  Taken: a float tensor [3, H, W] / [B, 3, H, W] in
+        [0, 1]; a uint8 tensor or numpy array [H, W, 3] / [B, H, W, 3]; a PIL image; a list of any of these (one image each).
+        Unlike diffusers' ``preprocess`` this only normalises and lays out NCHW: nothing is resized, and an image that is not
+        ``height`` x ``width`` is a ValueError (``hdr.prepare_sdr`` resizes and crops a picture on the device)."""
+        if isinstance(image, (list, tuple)):
+            if len(image) == 0:
+                raise ValueError("`image` is an empty list")
+            return torch.cat([self.preprocess(im, height, width) for im in image], 0)
+        if not torch.is_tensor(image):
+            arr = np.array(image)  # (a copy: a PIL image's buffer is read-only)
+            if arr.dtype != np.uint8:
+                raise ValueError(f"`image` as an array or PIL image must be uint8 RGB (got dtype {arr.dtype}); pass floats as a"
+                                 " [B, 3, H, W] tensor in [0, 1]")
+            image = torch.from_numpy(np.ascontiguousarray(arr))
+        if image.dtype == torch.uint8:
+            if image.dim() == 3:
+                image = image[None]
+            if image.dim() != 4 or image.shape[-1] != 3:
+                raise ValueError(f"a uint8 `image` must be [H, W, 3] or [B, H, W, 3] (got {tuple(image.shape)})")
+            image = image.permute(0, 3, 1, 2).to(torch.float32) / 255.0
+        elif image.is_floating_point():
+            if image.dim() == 3:
+                image = image[None]
+            if image.dim() != 4 or image.shape[1] != 3:
+                raise ValueError(f"a float `image` must be [3, H, W] or [B, 3, H, W] in [0, 1] (got {tuple(image.shape)})")
+            image = image.to(torch.float32)
+        else:
+            raise ValueError(f"`image` must be uint8 or floating point (got {image.dtype})")
+        if height is not None and width is not None and tuple(image.shape[-2:]) != (int(height), int(width)):
+            raise ValueError(f"`image` is {image.shape[-2]} x {image.shape[-1]} but this call is {height} x {width} (height x width);"
+                             " nothing is resized here: resize and crop the picture with gm_diffusion.hdr.prepare_sdr first")
+        image = self.normalize(image) if self.config.do_normalize else image
+        return image.contiguous()
+
     def postprocess(self, image, output_type="pil", do_denormalize=None):
         if not torch.is_tensor(image):
             raise ValueError(f"Input for postprocessing is in incorrect format: {type(image)}. Only pytorch tensor is supported")

@@ -8,7 +8,9 @@ classes keep the protocol the pipelines rely on (stable_diffusion_gm.py:216-241,
 1037, 1048, 1071; stable_diffusion_dual_unet.py:1037, 1072): ``config`` (dict-like, attribute
 access), ``set_timesteps``, ``timesteps``, ``order``, ``init_noise_sigma``,
 ``scale_model_input``, ``step(...)``, ``alphas_cumprod``, ``from_config`` and survival under
-``copy.deepcopy``.
+``copy.deepcopy``; for img2img and inpainting also diffusers' ``add_noise`` (every class), ``set_begin_index`` / ``begin_index`` (the
+classes that select a step by ``step_index``) and the host query ``add_noise_coefs(t)``: the float32 pair with
+``add_noise == ca * x + cb * noise`` that the fused blend kernel takes.
 
 The schedulers are host-side state machines; the per-element update runs in the
 ``gmd_latent_step`` HIP kernel for device tensors (same float32 operation order as the torch
@@ -109,6 +111,56 @@ class _SchedulerBase(ConfigMixin):
     def _x0_coefs(a):
         """(sqrt(a), sqrt(1 - a)) of the pipeline's own x0 (dual_unet.py:1072-1075), from ``alphas_cumprod`` of the loop timestep."""
         return a.sqrt().item(), (1 - a).sqrt().item()
+
+    # ---- forward noising: where img2img starts and what inpainting keeps (diffusers' ``add_noise``) ----------------------------------
+    def add_noise_coefs(self, timestep):
+        """The two float32 values ``(ca, cb)``, as Python floats, with ``add_noise(x, noise, [timestep]) == ca * x + cb * noise``: what
+        the pipelines hand to ``hip_ops.inpaint_blend``.  Here the variance-preserving pair of diffusers' PNDM / DDPM / DDIM / LCM
+        classes, ``alphas_cumprod[t] ** 0.5`` and ``(1 - alphas_cumprod[t]) ** 0.5`` on the float32 table."""
+        a = self.alphas_cumprod[int(timestep)]
+        return (a ** 0.5).item(), ((1 - a) ** 0.5).item()
+
+    @staticmethod
+    def _per_sample(coef, like):
+        """A per-timestep coefficient [n] shaped to broadcast over ``like`` ([n | any, ...]), as diffusers does it."""
+        coef = coef.flatten()
+        while coef.dim() < like.dim():
+            coef = coef.unsqueeze(-1)
+        return coef
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' ``add_noise`` of the variance-preserving classes: ``timesteps`` holds one integer timestep, or one per sample."""
+        timesteps = torch.as_tensor(timesteps).reshape(-1).to(device=original_samples.device, dtype=torch.long)
+        alphas_cumprod = self.alphas_cumprod.to(device=original_samples.device, dtype=original_samples.dtype)
+        sqrt_alpha_prod = self._per_sample(alphas_cumprod[timesteps] ** 0.5, original_samples)
+        sqrt_one_minus_alpha_prod = self._per_sample((1 - alphas_cumprod[timesteps]) ** 0.5, original_samples)
+        return sqrt_alpha_prod * original_samples + sqrt_one_minus_alpha_prod * noise
+
+
+class _StepIndexMixin:
+    """What the classes that select a step by ``step_index`` share beyond it: diffusers' ``set_begin_index`` / ``begin_index`` (an
+    img2img pipeline enters the schedule part-way down and says so before the first ``step``) and the index rule of ``add_noise``.
+    ``set_timesteps`` resets the begin index, as in diffusers.  A class gives ``_index_for_timestep``."""
+
+    _begin_index = None
+
+    @property
+    def begin_index(self):
+        return self._begin_index
+
+    def set_begin_index(self, begin_index=0):
+        self._begin_index = int(begin_index)
+
+    def _init_step_index(self, timestep):
+        self._step_index = self._index_for_timestep(timestep) if self._begin_index is None else self._begin_index
+
+    def _noise_indices(self, timesteps):
+        """diffusers' rule: no begin index (training, or a pipeline that sets none) -> the timestep's own entry; a step index already
+        set -> that one (the inpaint re-noise after a step, to the level of the next one); otherwise the begin index (the start of
+        img2img, before the first step)."""
+        if self._begin_index is None:
+            return [self._index_for_timestep(t) for t in timesteps]
+        return [self._begin_index if self._step_index is None else self._step_index] * len(timesteps)
 
 
 class PNDMScheduler(_SchedulerBase):
@@ -510,7 +562,7 @@ class LCMSchedulerOutput(_Output):
     denoised: torch.Tensor = None
 
 
-class LCMScheduler(_SchedulerBase):
+class LCMScheduler(_StepIndexMixin, _SchedulerBase):
     """Latent-consistency (LCM) multistep sampling: the few-step scheduler (2-8 steps) of a guidance-embedded UNet (config
     ``time_cond_proj_dim``; the branch of the reference pipelines at stable_diffusion_gm.py:1028-1034), which runs without the
     classifier-free-guidance duplicate.  Restates diffusers' ``LCMScheduler`` for epsilon prediction with ``clip_sample``;
@@ -592,13 +644,14 @@ class LCMScheduler(_SchedulerBase):
         self.timesteps = torch.from_numpy(ts).to(device=device, dtype=torch.long)
         self._ts_host = [int(v) for v in ts]
         self._step_index = None
+        self._begin_index = None
 
-    def _init_step_index(self, timestep):
+    def _index_for_timestep(self, timestep):
         t = int(timestep)
         idx = [k for k, v in enumerate(self._ts_host) if v == t]
         if not idx:
             raise ValueError(f"timestep {t} is not in the schedule {self._ts_host}")
-        self._step_index = idx[1] if len(idx) > 1 else idx[0]
+        return idx[1] if len(idx) > 1 else idx[0]
 
     predraws_noise = True
 
@@ -682,7 +735,7 @@ class LCMScheduler(_SchedulerBase):
         return (prev, denoised) if not return_dict else LCMSchedulerOutput(prev_sample=prev, denoised=denoised)
 
 
-class _MultistepSolverBase(_SchedulerBase):
+class _MultistepSolverBase(_StepIndexMixin, _SchedulerBase):
     """What ``DPMSolverMultistepScheduler`` and ``UniPCMultistepScheduler`` share (same config keys, same arithmetic): the state a
     constructor leaves, the timestep / sigma tables of ``set_timesteps``, the step-index rule and sigma -> (alpha_t, sigma_t)."""
 
@@ -729,19 +782,36 @@ class _MultistepSolverBase(_SchedulerBase):
         self.model_outputs = [None] * c.solver_order
         self.lower_order_nums = 0
         self._step_index = None
+        self._begin_index = None
 
     @staticmethod
     def _sigma_to_alpha_sigma_t(sigma):
         alpha_t = 1 / ((sigma ** 2 + 1) ** 0.5)
         return alpha_t, sigma * alpha_t
 
-    def _init_step_index(self, timestep):
+    def _index_for_timestep(self, timestep):
         t = int(timestep)
         idx = [k for k, v in enumerate(self._ts_host) if v == t]
         if not idx:
-            self._step_index = len(self._ts_host) - 1
-        else:
-            self._step_index = idx[1] if len(idx) > 1 else idx[0]
+            return len(self._ts_host) - 1
+        return idx[1] if len(idx) > 1 else idx[0]
+
+    def _noise_sigmas(self, timesteps):
+        """``sigmas[index]`` of ``add_noise``'s index rule, one float32 entry per timestep."""
+        if self.num_inference_steps is None:
+            raise ValueError("Number of inference steps is 'None', you need to run 'set_timesteps' after creating the scheduler")
+        return self.sigmas[self._noise_indices(timesteps)]
+
+    def add_noise_coefs(self, timestep):
+        """``(alpha_t, sigma_t)`` of ``sigmas[index]`` (diffusers' DPM-Solver / UniPC ``add_noise``), the index by ``_noise_indices``."""
+        alpha_t, sigma_t = self._sigma_to_alpha_sigma_t(self._noise_sigmas([timestep])[0])
+        return alpha_t.item(), sigma_t.item()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' ``add_noise`` of the DPM-Solver / UniPC classes: ``alpha_t * x + sigma_t * noise`` from ``sigmas[index]``."""
+        sigma = self._noise_sigmas(torch.as_tensor(timesteps).reshape(-1)).to(device=original_samples.device, dtype=original_samples.dtype)
+        alpha_t, sigma_t = self._sigma_to_alpha_sigma_t(self._per_sample(sigma, original_samples))
+        return alpha_t * original_samples + sigma_t * noise
 
 
 class DPMSolverMultistepScheduler(_MultistepSolverBase):
@@ -924,7 +994,7 @@ class EulerSchedulerOutput(_Output):
     pred_original_sample: torch.Tensor = None
 
 
-class _SigmaSchedulerBase(_SchedulerBase):
+class _SigmaSchedulerBase(_StepIndexMixin, _SchedulerBase):
     """What the sigma-space (variance-exploding) schedulers share: the sigma / timestep tables of diffusers' ``set_timesteps``
     (float64 numpy, stored as float32 tensors), ``init_noise_sigma``, ``scale_model_input`` and the step index.  Unlike the
     variance-preserving schedulers above, the UNet input is ``sample / (sigma**2 + 1) ** 0.5`` and the timesteps are float32,
@@ -1032,6 +1102,7 @@ class _SigmaSchedulerBase(_SchedulerBase):
         self.timesteps = torch.from_numpy(ts32).to(device=device)
         self._ts_host = torch.from_numpy(ts32).tolist()
         self._step_index = None
+        self._begin_index = None
 
     @staticmethod
     def _convert_to_karras(in_sigmas, num_inference_steps):
@@ -1042,14 +1113,24 @@ class _SigmaSchedulerBase(_SchedulerBase):
         min_inv_rho, max_inv_rho = sigma_min ** (1 / rho), sigma_max ** (1 / rho)
         return (max_inv_rho + ramp * (min_inv_rho - max_inv_rho)) ** rho
 
-    def _init_step_index(self, timestep):
+    def _index_for_timestep(self, timestep):
         """The entry equal to ``timestep`` as a float32 value (``set_timesteps`` refuses a schedule in which one occurs twice)."""
         t = float(timestep)
         idx = [k for k, v in enumerate(self._ts_host) if v == t]
         if not idx:
             raise ValueError(f"{self._name}: timestep {t!r} is not in the schedule set by `set_timesteps` (timesteps are float32"
                              " values and may be fractional: pass them on unchanged)")
-        self._step_index = idx[0]
+        return idx[0]
+
+    def add_noise_coefs(self, timestep):
+        """``(1, sigmas[index])``: in sigma space ``add_noise`` is ``x + noise * sigma``, the index by ``_noise_indices``."""
+        return 1.0, self.sigmas[self._noise_indices([timestep])[0]].item()
+
+    def add_noise(self, original_samples, noise, timesteps):
+        """diffusers' ``add_noise`` of the sigma-space classes: ``x + noise * sigmas[index]``."""
+        sigma = self.sigmas[self._noise_indices(torch.as_tensor(timesteps).reshape(-1))]
+        sigma = self._per_sample(sigma.to(device=original_samples.device, dtype=original_samples.dtype), original_samples)
+        return original_samples + noise * sigma
 
     def _sigma(self, timestep):
         """The current step's sigma as a float32 0-d tensor (fixes the step index from ``timestep`` on first use)."""

@@ -1538,6 +1538,25 @@ def cfg_std_ratio(eps_pair, guidance_scale):
     return ratio
 
 
+def inpaint_blend(z0, x_prev=None, x0=None, mask=None, noise=None, coefs=(1.0, 0.0)):
+    """The img2img start / inpaint blend of one step as ONE launch (gmd_inpaint_blend), in place on ``x_prev`` and ``x0``:
+    ``keep = ca * z0 + cb * noise`` (``z0`` itself without ``noise``), ``x_prev = (1 - m) * keep + m * x_prev`` (``keep`` without a
+    mask: ``x_prev`` is then written, never read) and ``x0 = (1 - m) * z0 + m * x0``.  z0 / noise / x_prev / x0: float32
+    [B, C, h, w]; mask: float32 [1 | B, 1, h, w]; coefs = (ca, cb) of the scheduler's ``add_noise_coefs``.  Returns (x_prev, x0)."""
+    _dev(z0, x_prev, x0, mask, noise)
+    for t in (z0, x_prev, x0, mask, noise):
+        _f32(t, "latent tensors")
+    if z0.dim() != 4 or _shape_differs(z0, x_prev, x0, noise):
+        raise HipExtensionError("inpaint_blend: z0 must be [B, C, h, w] and x_prev, x0 and noise must have its shape")
+    B, C, h, w = z0.shape
+    if mask is not None and (mask.dim() != 4 or mask.shape[1:] != (1, h, w)):
+        raise HipExtensionError(f"inpaint_blend: mask must be [1 | {B}, 1, {h}, {w}] (got {tuple(mask.shape)})")
+    ca, cb = (float(v) for v in coefs)
+    check(lib().gmd_inpaint_blend(_ptr(x_prev), _ptr(x0), _ptr(mask), _ptr(z0), _ptr(noise), B, C, h * w,
+                                  1 if mask is None else mask.shape[0], ca, cb, _stream()), "gmd_inpaint_blend")
+    return x_prev, x0
+
+
 def _shape_differs(x, *tensors):
     return any(t is not None and t.shape != x.shape for t in tensors)
 

@@ -70,6 +70,34 @@ hands the same ``added_cond_kwargs`` to both UNets (:1058, :1090), which only ru
 the positive rows if and only if an adapter was loaded into it (``pipe.gm_unet.load_ip_adapter``).  The scale lives in device memory:
 ``set_ip_adapter_scale`` between two calls needs no new capture.  Plus / FaceID variants, several adapters, ``ip_adapter_masks`` and
 per-block scales are refused by name.
+
+img2img and inpainting (diffusers' ``image``, ``strength``, ``mask_image``; the reference has neither): reached only when ``image`` is
+given.  Without it nothing changes, and ``mask_image`` or ``strength`` alone is a ValueError.
+  ``image``       float tensor [1 | rows, 3, H, W] in [0, 1], or uint8 [.., H, W, 3] tensor / array / PIL image or a list of them
+                  (``VaeImageProcessor.preprocess``: normalise and lay out only; another size than the call's is a ValueError, resize
+                  with ``hdr.prepare_sdr``), or [1 | rows, 4, h, w] latents already multiplied by ``scaling_factor``.  rows = batch x
+                  ``num_images_per_prompt``; one image is repeated.  Pixels become ``z0 = vae.encode(x).latent_dist.sample(generator)
+                  * scaling_factor`` in float32.
+  ``strength``    default 0.8, 1.0 with a mask; outside [0, 1] or ``int(num_inference_steps * strength) < 1`` is a ValueError.
+  ``mask_image``  [1 | rows, 1, H, W] or [H, W]; float, uint8 (255 = 1) or PIL "L"; 1 = repaint, 0 = keep.  Binarised at 0.5 and
+                  brought to latent size by ``F.interpolate`` (nearest), as diffusers' ``prepare_mask_latents``; a float mask
+                  [1 | rows, 1, h, w] of latent size is taken as it is.  4-channel SDR UNets only.
+Schedule (diffusers' ``get_timesteps``): ``t_start = max(N - min(int(N * strength), N), 0)``; the SDR branch runs
+``timesteps[t_start * order:]`` and its scheduler gets ``set_begin_index(t_start * order)``.  ``LCMScheduler`` takes ``strength`` in
+``set_timesteps`` instead and nothing is sliced.  ``noise = randn_tensor(latent shape, generator)`` (a given ``latents=`` is that
+noise); the generator serves the encoder's sample (pixels only), then ``noise``, then the steps' own draws.  The SDR latents start as
+``scheduler.add_noise(z0, noise, timesteps[:1])``; with a mask at strength 1.0 as ``noise * init_noise_sigma``.
+The GM branch has no picture to start from, and a gain map started part-way down the schedule from pure noise is outside what the GM
+UNet was trained on.  So the GM scheduler (the deep copy taken before ``set_begin_index``) always runs the WHOLE schedule from
+``noise * init_noise_sigma``: for the first ``t_start * order`` iterations the GM UNet runs alone with ``z0`` as its SDR operand --
+what ``StableDiffusionGMPipeline`` feeds it for a photograph -- and from then on the loop is the joint loop above.  Per iteration a
+shared generator is consumed by the GM scheduler alone at first, SDR before GM afterwards.
+Mask, after every SDR step i (diffusers' inpaint rule): ``keep = add_noise(z0, noise, timesteps[i + 1])`` (``z0`` at the last step),
+``latents = (1 - m) * keep + m * latents``; and the x0 handed to the GM UNet is ``(1 - m) * z0 + m * x0``: where the picture is kept
+it is known, so the gain map sees it.  The schedulers' multistep history is not blended (nor is it in diffusers).  Fused path: ONE
+launch per step (gmd_inpaint_blend, in place on the step's two outputs, on the SDR stream before the GM stream waits for x0); mask,
+z0 and noise are written once, outside any graph.  The generic loop does the same in torch expressions.  Refused by name: a mask with
+an SDR UNet of ``in_channels == 9`` (inpainting checkpoints), ``padding_mask_crop``, ``masked_image_latents``.
 """
 from __future__ import annotations
 
@@ -275,6 +303,59 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         return dict(text_embeds=torch.cat([added_cond["negative_text_embeds"].to(device), pos["text_embeds"]]),
                     time_ids=torch.cat([neg_ids, pos["time_ids"]])), pos
 
+    # ---- img2img / inpainting (see the module docstring) ---------------------------------------------------------------------------
+    def _encode_init_image(self, image, height, width, rows, shape, dtype, device, generator):
+        """``z0`` [rows, 4, h, w] of ``dtype`` on ``device``: the clean latents of ``image``, already multiplied by
+        ``scaling_factor``.  A tensor with 4 channels is taken as such latents (diffusers); anything else goes through
+        ``VaeImageProcessor.preprocess`` and ``vae.encode(x).latent_dist.sample(generator)``: the call's first draw."""
+        if torch.is_tensor(image) and image.dim() == 4 and image.shape[1] == 4:
+            z0 = image.to(device=device, dtype=dtype)
+        else:
+            from ..components.autoencoder_kl import AutoencoderKL
+
+            if isinstance(self.vae, AutoencoderKL) and ops.is_half(self.vae.dtype):
+                raise ValueError(f"`image` as pixels needs a float32 AutoencoderKL (this one is {self.vae.dtype}: its encoder's 8-channel"
+                                 " quant_conv is no 16-bit matrix-core shape); encode the picture with a float32 copy and pass the latents"
+                                 " (`vae.encode(x).latent_dist.sample(generator) * vae.config.scaling_factor`) as `image`")
+            x = self.image_processor.preprocess(image, height, width).to(device)
+            if isinstance(generator, list) and x.shape[0] == 1 and rows > 1:
+                x = x.expand(rows, -1, -1, -1).contiguous()  # one draw per generator
+            z0 = self.vae.encode(x).latent_dist.sample(generator).to(dtype) * self.vae.config.scaling_factor
+        if z0.shape[0] == 1 and rows > 1:
+            z0 = z0.expand(rows, -1, -1, -1)
+        if tuple(z0.shape) != tuple(shape):
+            raise ValueError(f"`image` gives latents of shape {tuple(z0.shape)} for this call's {tuple(shape)} (rows = batch x "
+                             "num_images_per_prompt; one image is repeated)")
+        return z0.contiguous()
+
+    @staticmethod
+    def _prepare_inpaint_mask(mask, height, width, h, w, rows, device):
+        """float32 [1 | rows, 1, h, w], 1 = repaint, 0 = keep.  An image-size mask ([H, W] or [1 | rows, 1, H, W]: float, uint8 with
+        255 = 1, PIL "L") is binarised at 0.5 and brought to latent size with ``F.interpolate`` (nearest), as diffusers'
+        ``prepare_mask_latents`` does; a float mask that already has the latent size is taken as it is."""
+        if not torch.is_tensor(mask):
+            import numpy as np
+
+            mask = torch.from_numpy(np.ascontiguousarray(np.array(mask)))  # (a copy: a PIL image's buffer is read-only)
+        if mask.dtype == torch.uint8:
+            mask = mask.to(torch.float32) / 255.0
+        elif mask.dtype == torch.bool:
+            mask = mask.to(torch.float32)
+        elif not mask.is_floating_point():
+            raise ValueError(f"`mask_image` must be float, uint8 or bool (got {mask.dtype})")
+        mask = mask.to(torch.float32)
+        if mask.dim() == 2:
+            mask = mask[None, None]
+        if mask.dim() != 4 or mask.shape[1] != 1 or mask.shape[0] not in (1, rows):
+            raise ValueError(f"`mask_image` must be [H, W] or [1 | {rows}, 1, H, W] (got {tuple(mask.shape)})")
+        if tuple(mask.shape[-2:]) != (h, w):
+            if tuple(mask.shape[-2:]) != (height, width):
+                raise ValueError(f"`mask_image` must be {height} x {width} (this call) or {h} x {w} (its latents); got"
+                                 f" {mask.shape[-2]} x {mask.shape[-1]}")
+            mask = (mask >= 0.5).to(torch.float32)
+            mask = torch.nn.functional.interpolate(mask, size=(h, w))
+        return mask.to(device).contiguous()
+
     def _gm_stream(self, device):
         return ops.side_stream(device)  # one per device for the whole process, not per pipeline object (see there)
 
@@ -313,6 +394,22 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         # added_cond_kwargs = {"text_embeds", "time_ids"[, "negative_text_embeds", "negative_time_ids"]}; every other unknown
         # keyword is ignored as in the reference
         added_cond = kwargs.pop("added_cond_kwargs", None)
+        # img2img / inpainting (module docstring): diffusers' keywords, read here and given meaning only when `image` is there
+        image, strength, mask_image = kwargs.pop("image", None), kwargs.pop("strength", None), kwargs.pop("mask_image", None)
+        for refused in ("padding_mask_crop", "masked_image_latents"):
+            if kwargs.pop(refused, None) is not None:
+                raise NotImplementedError(f"`{refused}` is not implemented: the inpainting of this pipeline keeps a region of the"
+                                          " latents of a 4-channel SDR UNet (`image`, `mask_image`, `strength`)")
+        if image is None and (mask_image is not None or strength is not None):
+            raise ValueError("`mask_image` and `strength` belong to img2img / inpainting: they need `image`")
+        if image is not None:
+            if mask_image is not None and self.unet.config.in_channels != 4:
+                raise NotImplementedError(f"`mask_image` with an SDR UNet of in_channels == {self.unet.config.in_channels} is not implemented"
+                                          " (9-channel inpainting checkpoints take the mask and the masked image as UNet input):"
+                                          " the mask keeps a region of the latents of a 4-channel UNet")
+            strength = float(strength) if strength is not None else (0.8 if mask_image is None else 1.0)
+            if not 0.0 <= strength <= 1.0:
+                raise ValueError(f"The value of strength should in [0.0, 1.0] but is {strength}")
         if hasattr(callback_on_step_end, "tensor_inputs"):
             callback_on_step_end_tensor_inputs = callback_on_step_end.tensor_inputs
         height, width = self._default_hw(height, width)
@@ -363,12 +460,50 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         if image_rows is not None and self.gm_unet.has_ip_adapter:
             gm_image_rows = image_rows[image_rows.shape[0] // 2:] if do_cfg else image_rows
 
-        timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas)
+        sdr_from = 0  # the iteration the SDR branch enters the loop at: 0 without `image`
+        if image is None:
+            timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas)
+        else:
+            from ..components.schedulers import LCMScheduler
+
+            if num_inference_steps is not None and int(num_inference_steps * strength) < 1:
+                raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of pipeline"
+                                 f" steps is {int(num_inference_steps * strength)} which is < 1 and not appropriate for this pipeline.")
+            if isinstance(self.scheduler, LCMScheduler):  # the LCM schedule is built for the strength: nothing to slice
+                timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas,
+                                                                    strength=strength)
+            else:
+                timesteps, num_inference_steps = retrieve_timesteps(self.scheduler, num_inference_steps, device, timesteps, sigmas)
+                init_timestep = min(int(num_inference_steps * strength), num_inference_steps)  # diffusers' get_timesteps
+                if init_timestep < 1:
+                    raise ValueError(f"After adjusting the num_inference_steps by strength parameter: {strength}, the number of"
+                                     f" pipeline steps is {init_timestep} which is < 1 and not appropriate for this pipeline.")
+                sdr_from = max(num_inference_steps - init_timestep, 0) * self.scheduler.order
 
         num_channels_latents = self.unet.config.in_channels
-        latents = self.prepare_latents(batch_size * num_images_per_prompt, num_channels_latents, height, width,
-                                       self._latent_dtype(prompt_embeds, device), device, generator, latents)
-        gm_latents = latents.clone()  # dual.py:1012: both streams start from the same (scaled) noise
+        z0 = noise = inpaint_mask = None
+        if image is None:
+            latents = self.prepare_latents(batch_size * num_images_per_prompt, num_channels_latents, height, width,
+                                           self._latent_dtype(prompt_embeds, device), device, generator, latents)
+            gm_latents = latents.clone()  # dual.py:1012: both streams start from the same (scaled) noise
+        else:
+            from ..components.image_processor import randn_tensor
+
+            n_rows, lat_dtype = batch_size * num_images_per_prompt, self._latent_dtype(prompt_embeds, device)
+            shape = (n_rows, num_channels_latents, int(height) // self.vae_scale_factor, int(width) // self.vae_scale_factor)
+            if isinstance(generator, list) and len(generator) != n_rows:
+                raise ValueError(f"You have passed a list of generators of length {len(generator)}, but requested an effective batch"
+                                 f" size of {n_rows}. Make sure the batch size matches the length of the generators.")
+            # generator order: the encoder's sample (pixels only), the noise, then the steps' own draws
+            z0 = self._encode_init_image(image, height, width, n_rows, shape, lat_dtype, device, generator)
+            noise = (randn_tensor(shape, generator=generator, device=device, dtype=lat_dtype) if latents is None
+                     else latents.to(device)).contiguous()
+            if mask_image is not None:
+                inpaint_mask = self._prepare_inpaint_mask(mask_image, height, width, shape[2], shape[3], n_rows, z0.device).to(lat_dtype)
+            # the GM branch has no picture to start from: it runs the whole schedule from the noise.  The SDR start needs the begin
+            # index, which is set below, after the GM scheduler was copied: until then `latents` stands for its shape and dtype
+            gm_latents = noise * self.scheduler.init_noise_sigma
+            latents = gm_latents
         extra_step_kwargs = self.prepare_extra_step_kwargs(generator, eta)
         # dual.py:1024-1030: the guidance-scale embedding of a guidance-embedded (LCM) UNet, each UNet at its own width (see the module
         # docstring); do_classifier_free_guidance is False for such an SDR UNet
@@ -383,9 +518,20 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
         sdr_added, gm_added = self._batched_added_cond(added_cond, do_cfg, latents.device)
         ip_ctx = gm_ip_ctx = None
         fused = self._use_fused(latents, self.unet, self.scheduler) and self._use_fused(latents, self.gm_unet, self.gm_scheduler)
+        if image is not None:
+            # the SDR branch enters the schedule at `sdr_from` (the GM scheduler, copied above, runs all of it)
+            if hasattr(self.scheduler, "set_begin_index") and not isinstance(self.scheduler, LCMScheduler):
+                self.scheduler.set_begin_index(sdr_from)
+            if inpaint_mask is not None and strength == 1.0:  # diffusers' is_strength_max: pure noise, the picture only where kept
+                latents = noise * self.scheduler.init_noise_sigma
+            elif fused:
+                latents = ops.inpaint_blend(z0, x_prev=torch.empty_like(z0), noise=noise,
+                                            coefs=self.scheduler.add_noise_coefs(timesteps[sdr_from]))[0]
+            else:
+                latents = self.scheduler.add_noise(z0, noise, timesteps[sdr_from:sdr_from + 1])
         keep = None  # per step: does the ControlNet run (diffusers' control guidance window); None without a controlnet
         if cn is not None:
-            keep = self._control_keep(len(timesteps), cg_start, cg_end)
+            keep = self._control_keep(len(timesteps) - sdr_from, cg_start, cg_end)  # over the SDR branch's steps: keep[i - sdr_from]
             cn_half = guess_mode and do_cfg  # guess mode: the ControlNet sees the conditional half only
             control_image = control_image.to(latents.device)
             if do_cfg and not cn_half:
@@ -441,12 +587,14 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     g_sdr_c = self.unet.graphed_forward(nb_sdr, h, w, ctx, cfg_shared=shared, co_run=co_run, control=control, ip=ip_ctx)
                 g_gm = self.gm_unet.graphed_forward(latents.shape[0], h, w, gm_ctx, co_run=co_run, ip=gm_ip_ctx)
             pre = self._predraw_step_noise([self.scheduler, self.gm_scheduler], ts_host, latents.shape, generator, latents.device,
-                                           eta=extra_step_kwargs.get("eta", 0.0))
+                                           eta=extra_step_kwargs.get("eta", 0.0), **({"first": (sdr_from, 0)} if sdr_from else {}))
             gm_stream.wait_stream(sdr_stream)
             if gm_stream is not sdr_stream:
                 # allocated on the caller's stream, consumed (and released) by step 0 on the GM stream: without this the
                 # allocator may hand the block to the SDR stream's step 1 while GM step 0 still reads it
                 gm_latents.record_stream(gm_stream)
+                if sdr_from:
+                    z0.record_stream(gm_stream)  # the GM UNet's SDR operand while the SDR branch waits
         elif image_rows is not None:
             # dual.py:1017-1022, 1058: added_cond_kwargs = {"image_embeds": [...]}, diffusers' list with one tensor per adapter
             sdr_added = {**(sdr_added or {}), "image_embeds": [image_rows.to(latents.device)]}
@@ -463,36 +611,46 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                 if self.interrupt:
                     continue
                 if fused:
-                    div = self._pack_div(self.scheduler, ts_host[i])
-                    use_cn = cn is not None and keep[i]  # inside the control guidance window: ControlNet, then the UNet's control graph
-                    g_step = g_sdr_c if use_cn else g_sdr
-                    x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_step.x if g_step else None,
-                                             **({"div": (div, 1.0)} if div is not None else {}))
-                    self.unet.set_timestep_from(ts_dev, i)
-                    if use_cn:  # the same latents and timestep, packed for the ControlNet's own batch
-                        cx = cn.pack_input(latents, dup=2 if (do_cfg and not cn_half) else 1, out=g_cn.x if g_cn else None,
-                                           **({"div": (div, 1.0)} if div is not None else {}))
-                        cn.set_timestep_from(ts_dev, i)
-                    if g_step:
-                        if use_cn:
-                            g_cn.replay()
-                        sdr_noise_pred = g_step.replay()
-                    elif use_cn:
-                        with ops.plan_family(co_run):
-                            c_down, c_mid = cn.forward_packed(cx, cn_rows, h, w, cn_ctx)
-                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx,
-                                                                      control=(c_down, c_mid, cn_scales, cn_skip))
-                    else:
-                        with ops.plan_family(co_run):
-                            sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx)
-                    pre_step = latents
-                    latents, x0_latent = self.scheduler.fused_step(sdr_noise_pred, ts_host[i], pre_step, do_cfg, self.guidance_scale,
-                                                                   self.guidance_rescale if do_cfg else 0.0, want_x0=True,
-                                                                   **self._fused_step_kwargs(extra_step_kwargs),
-                                                                   **({"noise": pre[0][i]} if pre else {}))
+                    if i >= sdr_from:  # (img2img: the GM branch runs alone until the SDR branch enters the schedule)
+                        div = self._pack_div(self.scheduler, ts_host[i])
+                        use_cn = cn is not None and keep[i - sdr_from]  # inside the control guidance window: ControlNet, then the UNet's control graph
+                        g_step = g_sdr_c if use_cn else g_sdr
+                        x = self.unet.pack_input(latents, dup=2 if (do_cfg and not shared) else 1, out=g_step.x if g_step else None,
+                                                 **({"div": (div, 1.0)} if div is not None else {}))
+                        self.unet.set_timestep_from(ts_dev, i)
+                        if use_cn:  # the same latents and timestep, packed for the ControlNet's own batch
+                            cx = cn.pack_input(latents, dup=2 if (do_cfg and not cn_half) else 1, out=g_cn.x if g_cn else None,
+                                               **({"div": (div, 1.0)} if div is not None else {}))
+                            cn.set_timestep_from(ts_dev, i)
+                        if g_step:
+                            if use_cn:
+                                g_cn.replay()
+                            sdr_noise_pred = g_step.replay()
+                        elif use_cn:
+                            with ops.plan_family(co_run):
+                                c_down, c_mid = cn.forward_packed(cx, cn_rows, h, w, cn_ctx)
+                                sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx,
+                                                                          control=(c_down, c_mid, cn_scales, cn_skip))
+                        else:
+                            with ops.plan_family(co_run):
+                                sdr_noise_pred = self.unet.forward_packed(x, nb_sdr, h, w, ctx, cfg_shared=shared, ip=ip_ctx)
+                        pre_step = latents
+                        latents, x0_latent = self.scheduler.fused_step(sdr_noise_pred, ts_host[i], pre_step, do_cfg, self.guidance_scale,
+                                                                       self.guidance_rescale if do_cfg else 0.0, want_x0=True,
+                                                                       **self._fused_step_kwargs(extra_step_kwargs),
+                                                                       **({"noise": pre[0][i]} if pre else {}))
+                        if inpaint_mask is not None:
+                            # diffusers' inpaint rule and the x0 the GM UNet sees, one launch on the SDR stream, in place on the
+                            # step's own outputs: the kept region returns to the picture at the next step's noise level
+                            last = i == len(ts_host) - 1
+                            ops.inpaint_blend(z0, x_prev=latents, x0=x0_latent, mask=inpaint_mask, noise=None if last else noise,
+                                              coefs=(1.0, 0.0) if last else self.scheduler.add_noise_coefs(ts_host[i + 1]))
                     with torch.cuda.stream(gm_stream):
-                        gm_stream.wait_stream(sdr_stream)  # x0_i is ready
-                        x0_latent.record_stream(gm_stream)
+                        if i >= sdr_from:
+                            gm_stream.wait_stream(sdr_stream)  # x0_i is ready
+                            x0_latent.record_stream(gm_stream)
+                        else:
+                            x0_latent = z0  # what StableDiffusionGMPipeline feeds the GM UNet: a picture's own latents
                         gm_div = self._pack_div(self.gm_scheduler, ts_host[i])  # x0 is a clean-image estimate: never scaled
                         gx = self.gm_unet.pack_input((x0_latent, gm_latents), dup=1, out=g_gm.x if g_gm else None,
                                                      **({"div": (1.0, gm_div)} if gm_div is not None else {}))
@@ -505,12 +663,20 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                         gm_latents = self.gm_scheduler.step(gm_noise_pred, ts_host[i], gm_latents,
                                                             **self._fused_step_kwargs(extra_step_kwargs),
                                                             **({"noise": pre[1][i]} if pre else {}), return_dict=False)[0]
+                elif i < sdr_from:
+                    # img2img: the GM branch alone, on the picture's own latents, until the SDR branch enters the schedule
+                    gm_latents = self.gm_scheduler.scale_model_input(gm_latents, t)
+                    gm_latent_input = torch.cat([z0, gm_latents], dim=1)
+                    gm_noise_pred = self.gm_unet(gm_latent_input, t, encoder_hidden_states=gm_prompt_embeds, timestep_cond=gm_timestep_cond,
+                                                 cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=gm_added,
+                                                 return_dict=False)[0]
+                    gm_latents = self.gm_scheduler.step(gm_noise_pred, t, gm_latents, **extra_step_kwargs, return_dict=False)[0]
                 else:
                     latent_model_input = torch.cat([latents] * 2) if do_cfg else latents
                     latent_model_input = self.scheduler.scale_model_input(latent_model_input, t)
                     gm_latents = self.gm_scheduler.scale_model_input(gm_latents, t)
                     cn_kw = {}
-                    if cn is not None and keep[i]:
+                    if cn is not None and keep[i - sdr_from]:
                         # diffusers' StableDiffusionControlNetPipeline: guess mode infers the conditional half only and pads the
                         # unconditional half's residuals with zeros
                         c_in = self.scheduler.scale_model_input(latents, t) if cn_half else latent_model_input
@@ -534,6 +700,12 @@ class StableDiffusionDualUNetPipeline(_GMPipelineBase):
                     sqrt_one_minus_alpha_cumprod = (1 - alphas_cumprod).sqrt()
                     x0_latent = (latents - sqrt_one_minus_alpha_cumprod * sdr_noise_pred) / sqrt_alpha_cumprod
                     latents = self.scheduler.step(sdr_noise_pred, t, latents, **extra_step_kwargs, return_dict=False)[0]
+                    if inpaint_mask is not None:
+                        # diffusers' inpaint rule: the kept region returns to the picture at the next step's noise level (the picture
+                        # itself at the last step); the GM UNet sees the clean picture where it is kept
+                        kept = z0 if i == len(timesteps) - 1 else self.scheduler.add_noise(z0, noise, timesteps[i + 1:i + 2])
+                        latents = (1 - inpaint_mask) * kept + inpaint_mask * latents
+                        x0_latent = (1 - inpaint_mask) * z0 + inpaint_mask * x0_latent
                     gm_latent_input = torch.cat([x0_latent, gm_latents], dim=1)
                     gm_noise_pred = self.gm_unet(gm_latent_input, t, encoder_hidden_states=gm_prompt_embeds, timestep_cond=gm_timestep_cond,
                                                  cross_attention_kwargs=self.cross_attention_kwargs, added_cond_kwargs=gm_added,

@@ -473,7 +473,7 @@ class _GMPipelineBase(DiffusionPipeline):
     PREDRAW_NOISE_BYTES = 512 << 20  # ceiling of the pre-drawn scheduler noise (host pinned copy + device copy)
 
     @staticmethod
-    def _predraw_step_noise(schedulers, ts_host, shape, generator, device, eta=0.0):
+    def _predraw_step_noise(schedulers, ts_host, shape, generator, device, eta=0.0, first=None):
         """Stochastic schedulers on the fused path with a CPU generator: draw the variance noise of EVERY step now, in exactly
         the order the loop would consume the generator (per iteration: the schedulers in the order given -- SDR before GM,
         stable_diffusion_dual_unet.py:1077, 1093), and move it to the device in one asynchronous copy.  A draw inside the
@@ -486,6 +486,9 @@ class _GMPipelineBase(DiffusionPipeline):
         ``DPMSolverMultistepScheduler`` with the SDE algorithm, and ``EulerAncestralDiscreteScheduler`` always; a deterministic
         scheduler (``EulerDiscreteScheduler``, ``LMSDiscreteScheduler`` and ``UniPCMultistepScheduler`` among them) has nothing to pre-draw.  ``LCMScheduler`` draws
         at every step but the last, as DDPM does.
+        ``first``: per scheduler, the iteration it takes its first step at (None: every scheduler steps from iteration 0).  The dual
+        pipeline's img2img loop steps the GM scheduler alone for the first iterations: per iteration the order is still the
+        schedulers' order, over those that step.
         Difference from the reference under ``interrupt``: the pre-draw has already advanced the caller's generator for the
         steps an interrupt later skips; the reference would not have consumed those draws."""
         if generator is None or not all(getattr(s_, "predraws_noise", False) for s_ in schedulers):
@@ -493,7 +496,8 @@ class _GMPipelineBase(DiffusionPipeline):
         gens = generator if isinstance(generator, list) else [generator]
         if any(g_.device.type != "cpu" for g_ in gens):
             return None
-        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers) if s_.draws_noise(t, eta)]
+        slots = [(i, k) for i, t in enumerate(ts_host) for k, s_ in enumerate(schedulers)
+                 if (first is None or i >= first[k]) and s_.draws_noise(t, eta)]
         if not slots:
             return None
         nbytes = 4 * len(slots)

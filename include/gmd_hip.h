@@ -315,6 +315,17 @@ int gmd_unipc_step(const float* eps_in, const float* x, const float* last_sample
 int gmd_cfg_std_ratio(const float* eps_in, int B, int64_t chw, float guidance_scale,
                       float* ratio, gmd_stream_t stream);
 
+/* img2img start and inpaint blend of one step over [B, C, hw] float32 latents, one launch for what torch writes as
+ *   keep   = scheduler.add_noise(z0, noise, t_next)  ==  ca * z0 + cb * noise     (noise == NULL, the last step: keep = z0)
+ *   x_prev = (1 - m) * keep + m * x_prev                                          (mask == NULL: x_prev = keep, x_prev is not read)
+ *   x0     = (1 - m) * z0 + m * x0                                                (x0 may be NULL)
+ * in that float32 operation order, no FMA contraction; m = mask[(mask_rows == 1 ? 0 : b) * hw + p], broadcast over the channels,
+ * any float value (1 = repaint, 0 = keep; no shortcut at 0 or 1, so 0 * inf is NaN as in torch).  x_prev and x0 are updated in
+ * place.  (ca, cb) come from the scheduler's add_noise_coefs.  B * C * hw == 0 is a no-op.  Refused before any launch: a null z0,
+ * both outputs null, x0 without a mask, mask_rows neither 1 nor B. */
+int gmd_inpaint_blend(float* x_prev, float* x0, const float* mask, const float* z0, const float* noise, int B, int C, int64_t hw,
+                      int mask_rows, float ca, float cb, gmd_stream_t stream);
+
 /* 8-channel concat + CFG duplicate + NCHW->NHWC + cast + zero channel padding in one pass
  * (stable_diffusion_gm.py:1045-1047 cat([sdr_latent, latents],1) then cat([.]*2);
  *  stable_diffusion_dual_unet.py:1045, 1080).  src0 [B,C0,HW] f32, src1 [B,C1,HW] f32 or NULL;
