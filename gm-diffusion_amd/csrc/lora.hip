@@ -28,6 +28,23 @@
 // output f = 8 (c >> 2) + 4 q + (c & 3), so lane (c, g) holds value AND gate of the 8 CONSECUTIVE outputs 8 g .. 8 g + 7 of row
 // 16 wid + c: two 16-byte loads of Y (whose 8 values and 8 gates are contiguous), one 16-byte store of F.  Y is read once and never
 // written, every element of F is written once by one lane; v, g, the GELU and the product stay in float32.
+//
+// SEVERAL adapters on one projection as ONE launch (gmd_lora_update_stacked / gmd_lora_geglu_stacked, STACKED of the same kernel):
+// Aw [Rp, K] and Bw [N, Rp] hold the adapters' factors side by side along the rank, the SUM of the ranks zero-padded to a multiple of
+// 32, Rp in {32, 64, ..., 256}; instead of scales[index] the kernel reads a float32 ROW of column scales, colscales + index * ldc,
+// Rp values long:
+//   That[m, j] = round16( colscale[j] * sum_k X[m, k] * Aw[j, k] )      float32 accumulate, the scale applied in float32, ONE rounding
+//   Y[m, n]   <- round16( float(Y[m, n]) + sum_j That[m, j] * Bw[n, j] )   float32 accumulate, one rounding on the store
+//   GEGLU:     v, g as above with  U = sum_j That * Bw  (no further scale)
+// The scale sits in front of That's one rounding: phase 2 -- the GEGLU's four MFMA chains included -- is the one above with s = 1, and
+// the cost is four multiplies per 16-wide rank block per lane.  The row of column scales is read from DEVICE memory once per workgroup
+// (thread j loads column j in front of the K loop and parks it in LDS; the lanes read their four columns per rank block back behind
+// the loop), so one captured graph serves every weight setting and no register is held across the loop.  A column whose sum is exactly
+// 0 -- every zero-padded column -- contributes exactly 0 whatever its table entry holds.  The summation orders are those of the
+// single-adapter launch: they depend on k and j only, never on the grid.  Rp = 160 .. 256 instantiates the same template wider
+// (45 - 72 KB of LDS, 116 - 190 VGPRs + 40 - 64 AGPRs, 2 - 3 waves per SIMD, no scratch: profiles/lora_multi.txt has the compiler's
+// resource report); the LDS row strides TROW = Rp / 2 + 4 dwords fall on the residues 20, 36, 52 and 4 (mod 64 banks), exactly those
+// of the widths up to 128, so the 16-byte row reads stay as conflict-free as they are there.
 #include "gmd_common.h"
 
 namespace {
@@ -40,7 +57,7 @@ struct LoraParams {
     const bf16_t* Bw;
     bf16_t* Y;           // MODE_GEGLU: read-only
     bf16_t* F;           // MODE_GEGLU only: the output [M, N / 2], row stride ldf
-    const float* scale;  // the entry this launch reads (array base + index)
+    const float* scale;  // the entry this launch reads (array base + index); STACKED: its row of Rp column scales
     int M, K, N;
     int tokens, tblocks;  // transposed mode: tokens per batch entry, 64-token blocks per batch entry
     int ldx, ldy, ldf;    // elements
@@ -56,17 +73,19 @@ constexpr int NT = 64;    // columns of Y per tile
 constexpr int KT = 64;    // K step
 constexpr int AROW = KT * 2 + 16;  // bytes per LDS row of an Aw tile: 36 dwords, conflict-free 16-byte row reads
 
-template <typename HT, int RP, int MODE>
+template <typename HT, int RP, int MODE, bool STACKED = false>
 __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
     GMD_WG_TRACE_SCOPE(WGK_OTHER);
+    static_assert(RP <= 128 || STACKED, "ranks above 128 are stacked launches");
     constexpr bool TRANS = MODE == MODE_TRANS;
     constexpr int NJ = RP / 16;        // 16-wide blocks of the rank
     constexpr int NK2 = RP / 32;       // k-steps of the second product; also 16-byte staging chunks per thread and tile
-    constexpr int TROW = RP * 2 + 16;  // bytes per LDS row of That and of a Bw tile: 20 / 36 / 52 / 68 dwords, conflict-free 16-byte row reads
+    constexpr int TROW = RP * 2 + 16;  // bytes per LDS row of That and of a Bw tile: 20 / 36 / 52 / 68 (stacked: ... / 132) dwords, conflict-free 16-byte row reads
     constexpr int kStage = (RP * AROW > NT * TROW) ? RP * AROW : NT * TROW;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[kStage + ROWS * TROW];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[kStage + ROWS * TROW + (STACKED ? RP * 4 : 0)];
     unsigned char* stage = smem;
     unsigned char* Ts = smem + kStage;
+    float* cs = reinterpret_cast<float*>(smem + kStage + ROWS * TROW);  // STACKED: the row of column scales
 
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
     const int c = lane & 15, g = lane >> 4;
@@ -125,8 +144,11 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
             }
         __syncthreads();  // the tile is consumed: the next step may overwrite it
     };
+    float csv = 0.f;  // STACKED: thread j brings column j's scale (RP <= 256 threads); visible behind the first K step's barrier
+    if (STACKED && tid < RP) csv = p.scale[tid];
     load_set(0, ar0, x0);
     load_set(min(KT, p.K - KT), ar1, x1);
+    if (STACKED && tid < RP) cs[tid] = csv;
     for (int k0 = 0; k0 < p.K; k0 += 2 * KT) {
         k_step(k0, ar0, x0);
         if (k0 + KT < p.K) k_step(k0 + KT, ar1, x1);
@@ -134,6 +156,12 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
     // the ONE rounding of That: row xr, columns 16 jb + 4 g + (0..3)
 #pragma unroll
     for (int jb = 0; jb < NJ; ++jb) {
+        if constexpr (STACKED) {  // the column scale in float32 in front of the rounding; an exact 0 (a padded column) stays 0
+            const float4 sc = *reinterpret_cast<const float4*>(cs + 16 * jb + 4 * g);
+            const float scv[4] = {sc.x, sc.y, sc.z, sc.w};
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tacc[jb][i] = tacc[jb][i] == 0.f ? 0.f : scv[i] * tacc[jb][i];
+        }
         uint2 w;
         w.x = Half<HT>::pack2(tacc[jb][0], tacc[jb][1]);
         w.y = Half<HT>::pack2(tacc[jb][2], tacc[jb][3]);
@@ -164,7 +192,7 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
         uint4 tf[NK2];  // That row xr, the B operand of every chain, held for the whole walk
 #pragma unroll
         for (int ks = 0; ks < NK2; ++ks) tf[ks] = *reinterpret_cast<const uint4*>(Ts + xr * TROW + (32 * ks + 8 * g) * 2);
-        const float s = *p.scale;
+        const float s = STACKED ? 1.f : *p.scale;  // STACKED: the scales are in That already (1 * u folds to u)
         const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)p.Y, 0, (int)p.ybytes, 0x00020000);
         const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)p.F, 0, (int)p.fbytes, 0x00020000);
         const bool valid = xr < rows_valid;
@@ -250,7 +278,7 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
 #pragma unroll
         for (int ks = 0; ks < NK2; ++ks) tf[h][ks] = *reinterpret_cast<const uint4*>(Ts + trow * TROW + (32 * ks + 8 * g) * 2);
     }
-    const float s = *p.scale;
+    const float s = STACKED ? 1.f : *p.scale;  // STACKED: the scales are in That already (1 * u folds to u)
     const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc((void*)(TRANS ? p.Y + (int64_t)bidx * p.strideY : p.Y), 0, (int)p.ybytes, 0x00020000);
 
     for (int t = t_begin; t < t_end; ++t) {
@@ -320,34 +348,36 @@ __global__ __launch_bounds__(256) void lora_update_kernel(const LoraParams p) {
     }
 }
 
-template <typename HT, int RP>
-int launch_lora(const LoraParams& p, bool trans, dim3 grid, hipStream_t s) {
-    if (trans) lora_update_kernel<HT, RP, MODE_TRANS><<<grid, 256, 0, s>>>(p);
-    else lora_update_kernel<HT, RP, MODE_PLAIN><<<grid, 256, 0, s>>>(p);
-    GMD_CHECK_LAUNCH("gmd_lora_update");
-    return GMD_OK;
+template <typename HT, int RP, bool STACKED>
+void launch_lora(const LoraParams& p, int mode, dim3 grid, hipStream_t s) {
+    if (mode == MODE_TRANS) lora_update_kernel<HT, RP, MODE_TRANS, STACKED><<<grid, 256, 0, s>>>(p);
+    else if (mode == MODE_GEGLU) lora_update_kernel<HT, RP, MODE_GEGLU, STACKED><<<grid, 256, 0, s>>>(p);
+    else lora_update_kernel<HT, RP, MODE_PLAIN, STACKED><<<grid, 256, 0, s>>>(p);
 }
 
+// the single-adapter launches: exactly the instantiations (and so the code objects) they have always been
 template <typename HT>
-int dispatch_lora(const LoraParams& p, int Rp, bool trans, dim3 grid, hipStream_t s) {
+void dispatch_lora(const LoraParams& p, int Rp, int mode, dim3 grid, hipStream_t s) {
     switch (Rp) {
-        case 32: return launch_lora<HT, 32>(p, trans, grid, s);
-        case 64: return launch_lora<HT, 64>(p, trans, grid, s);
-        case 96: return launch_lora<HT, 96>(p, trans, grid, s);
-        default: return launch_lora<HT, 128>(p, trans, grid, s);
+        case 32: return launch_lora<HT, 32, false>(p, mode, grid, s);
+        case 64: return launch_lora<HT, 64, false>(p, mode, grid, s);
+        case 96: return launch_lora<HT, 96, false>(p, mode, grid, s);
+        default: return launch_lora<HT, 128, false>(p, mode, grid, s);
     }
 }
 
 template <typename HT>
-int dispatch_lora_geglu(const LoraParams& p, int Rp, dim3 grid, hipStream_t s) {
+void dispatch_lora_stacked(const LoraParams& p, int Rp, int mode, dim3 grid, hipStream_t s) {
     switch (Rp) {
-        case 32: lora_update_kernel<HT, 32, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
-        case 64: lora_update_kernel<HT, 64, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
-        case 96: lora_update_kernel<HT, 96, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
-        default: lora_update_kernel<HT, 128, MODE_GEGLU><<<grid, 256, 0, s>>>(p); break;
+        case 32: return launch_lora<HT, 32, true>(p, mode, grid, s);
+        case 64: return launch_lora<HT, 64, true>(p, mode, grid, s);
+        case 96: return launch_lora<HT, 96, true>(p, mode, grid, s);
+        case 128: return launch_lora<HT, 128, true>(p, mode, grid, s);
+        case 160: return launch_lora<HT, 160, true>(p, mode, grid, s);
+        case 192: return launch_lora<HT, 192, true>(p, mode, grid, s);
+        case 224: return launch_lora<HT, 224, true>(p, mode, grid, s);
+        default: return launch_lora<HT, 256, true>(p, mode, grid, s);
     }
-    GMD_CHECK_LAUNCH("gmd_lora_geglu");
-    return GMD_OK;
 }
 
 // N tiles of 64 columns one workgroup walks: N is split over gridDim.y where the row blocks alone cannot fill the chip (256 CUs,
@@ -359,41 +389,60 @@ int tiles_per_y(int64_t gx, int ntiles) {
     return (ntiles + nsplit - 1) / nsplit;
 }
 
-}  // namespace
+// The table argument of both families: `table` + `index` is the one scale of a single-adapter launch; of a stacked launch
+// (ldc >= 0) `table` + index * ldc is its row of Rp column scales.
+struct ScaleArg {
+    const float* table;
+    int index;
+    int64_t ldc;  // < 0: a single-adapter launch
+    bool stacked() const { return ldc >= 0; }
+    const float* entry() const { return stacked() ? table + (int64_t)index * ldc : table + index; }
+};
 
-extern "C" int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
-                              int64_t ldx, int64_t ldy, int64_t ldf, const float* scales, int index, gmd_stream_t stream) {
+int check_rank_and_table(const char* fn, int Rp, const ScaleArg& sa) {
+    const int max_rp = sa.stacked() ? 256 : 128;
+    GMD_REQUIRE(Rp > 0 && Rp % 32 == 0, "%s: padded rank Rp=%d must be a positive multiple of 32", fn, Rp);
+    GMD_REQUIRE(Rp <= max_rp, "%s: padded rank Rp=%d above %d", fn, Rp, max_rp);
+    if (sa.stacked()) {
+        GMD_REQUIRE(sa.table != nullptr && sa.index >= 0, "%s: colscales must be a device array, the index non-negative", fn);
+        GMD_REQUIRE(sa.ldc >= Rp, "%s: ldc=%lld smaller than Rp=%d", fn, (long long)sa.ldc, Rp);
+    } else {
+        GMD_REQUIRE(sa.table != nullptr && sa.index >= 0, "%s: scales must be a device array, the index non-negative", fn);
+    }
+    return GMD_OK;
+}
+
+int lora_geglu_impl(const char* fn, const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                    int64_t ldx, int64_t ldy, int64_t ldf, const ScaleArg& sa, gmd_stream_t stream) {
     if (dtype != GMD_BF16 && dtype != GMD_F16) {
-        gmd_set_error("gmd_lora_geglu: GMD_BF16 / GMD_F16 are implemented (float32 composes gmd_gemm_nt twice, gmd_scaled_add and "
-                      "gmd_geglu / gmd_geglu_interleaved)");
+        gmd_set_error("%s: GMD_BF16 / GMD_F16 are implemented (float32 composes gmd_gemm_nt twice, gmd_scaled_add and "
+                      "gmd_geglu / gmd_geglu_interleaved)", fn);
         return GMD_ERR_UNSUPPORTED;
     }
-    GMD_REQUIRE(M >= 0 && C > 0, "gmd_lora_geglu: bad shape M=%d C=%d", M, C);
-    GMD_REQUIRE(C % 64 == 0, "gmd_lora_geglu: C=%d must be a multiple of 64", C);
-    GMD_REQUIRE(C <= (1 << 24), "gmd_lora_geglu: C=%d too large", C);
-    GMD_REQUIRE(Rp > 0 && Rp % 32 == 0, "gmd_lora_geglu: padded rank Rp=%d must be a positive multiple of 32", Rp);
-    GMD_REQUIRE(Rp <= 128, "gmd_lora_geglu: padded rank Rp=%d above 128", Rp);
-    GMD_REQUIRE(scales != nullptr && index >= 0, "gmd_lora_geglu: scales must be a device array, the index non-negative");
+    GMD_REQUIRE(M >= 0 && C > 0, "%s: bad shape M=%d C=%d", fn, M, C);
+    GMD_REQUIRE(C % 64 == 0, "%s: C=%d must be a multiple of 64", fn, C);
+    GMD_REQUIRE(C <= (1 << 24), "%s: C=%d too large", fn, C);
+    if (int rc = check_rank_and_table(fn, Rp, sa)) return rc;
     const int N = 8 * C, NF = 4 * C;
-    GMD_REQUIRE(ldx >= C && ldy >= N && ldf >= NF, "gmd_lora_geglu: ldx=%lld / ldy=%lld / ldf=%lld smaller than C=%d / 8C / 4C", (long long)ldx,
+    GMD_REQUIRE(ldx >= C && ldy >= N && ldf >= NF, "%s: ldx=%lld / ldy=%lld / ldf=%lld smaller than C=%d / 8C / 4C", fn, (long long)ldx,
                 (long long)ldy, (long long)ldf, C);
-    GMD_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && ldf % 8 == 0, "gmd_lora_geglu: leading dimensions must be multiples of 8");
+    GMD_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0 && ldf % 8 == 0, "%s: leading dimensions must be multiples of 8", fn);
     if (M == 0) return GMD_OK;  // nothing to write
-    GMD_REQUIRE(X && Aw && Bw && Y && F, "gmd_lora_geglu: null pointer");
+    GMD_REQUIRE(X && Aw && Bw && Y && F, "%s: null pointer", fn);
     GMD_REQUIRE(gmd_aligned16(X) && gmd_aligned16(Aw) && gmd_aligned16(Bw) && gmd_aligned16(Y) && gmd_aligned16(F),
-                "gmd_lora_geglu: pointers must be 16-byte aligned");
+                "%s: pointers must be 16-byte aligned", fn);
     const int64_t xbytes = (((int64_t)M - 1) * ldx + C) * 2, ybytes = (((int64_t)M - 1) * ldy + N) * 2, fbytes = (((int64_t)M - 1) * ldf + NF) * 2;
-    GMD_REQUIRE(xbytes < (1ll << 31) && ybytes < (1ll << 31) && fbytes < (1ll << 31), "gmd_lora_geglu: X, Y or F exceeds 2 GiB (32-bit byte offsets)");
+    GMD_REQUIRE(xbytes < (1ll << 31) && ybytes < (1ll << 31) && fbytes < (1ll << 31), "%s: X, Y or F exceeds 2 GiB (32-bit byte offsets)", fn);
     {
         const uintptr_t f0 = (uintptr_t)F, f1 = f0 + (uintptr_t)fbytes, x0 = (uintptr_t)X, x1 = x0 + (uintptr_t)xbytes, y0 = (uintptr_t)Y,
                         y1 = y0 + (uintptr_t)ybytes;
-        GMD_REQUIRE(x1 <= f0 || f1 <= x0, "gmd_lora_geglu: F overlaps X");
-        GMD_REQUIRE(y1 <= f0 || f1 <= y0, "gmd_lora_geglu: F overlaps Y");
+        GMD_REQUIRE(x1 <= f0 || f1 <= x0, "%s: F overlaps X", fn);
+        GMD_REQUIRE(y1 <= f0 || f1 <= y0, "%s: F overlaps Y", fn);
     }
     LoraParams p;
     p.X = (const bf16_t*)X; p.Aw = (const bf16_t*)Aw; p.Bw = (const bf16_t*)Bw; p.Y = (bf16_t*)const_cast<void*>(Y);
     p.F = (bf16_t*)F; p.ldf = (int)ldf; p.fbytes = (unsigned)fbytes;
-    p.scale = scales + index;
+    p.scale = sa.entry();
     p.M = M; p.K = C; p.N = N;
     p.tokens = M; p.tblocks = 0;
     p.ldx = (int)ldx; p.ldy = (int)ldy;
@@ -404,47 +453,47 @@ extern "C" int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, con
     p.tiles_per_y = tiles_per_y(gx, ntiles);
     dim3 grid((unsigned)gx, (unsigned)((ntiles + p.tiles_per_y - 1) / p.tiles_per_y), 1);
     hipStream_t s = (hipStream_t)stream;
-    return dtype == GMD_F16 ? dispatch_lora_geglu<f16_t>(p, Rp, grid, s) : dispatch_lora_geglu<bf16_t>(p, Rp, grid, s);
+    if (sa.stacked()) dtype == GMD_F16 ? dispatch_lora_stacked<f16_t>(p, Rp, MODE_GEGLU, grid, s) : dispatch_lora_stacked<bf16_t>(p, Rp, MODE_GEGLU, grid, s);
+    else dtype == GMD_F16 ? dispatch_lora<f16_t>(p, Rp, MODE_GEGLU, grid, s) : dispatch_lora<bf16_t>(p, Rp, MODE_GEGLU, grid, s);
+    GMD_CHECK_LAUNCH(fn);
+    return GMD_OK;
 }
 
-extern "C" int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N, int64_t ldx,
-                               int64_t ldy, int transposed, int batch, int tokens, int64_t strideY, const float* scales, int index,
-                               gmd_stream_t stream) {
+int lora_update_impl(const char* fn, const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N, int64_t ldx,
+                     int64_t ldy, int transposed, int batch, int tokens, int64_t strideY, const ScaleArg& sa, gmd_stream_t stream) {
     if (dtype != GMD_BF16 && dtype != GMD_F16) {
-        gmd_set_error("gmd_lora_update: GMD_BF16 / GMD_F16 are implemented (float32 composes gmd_gemm_nt twice and gmd_scaled_add)");
+        gmd_set_error("%s: GMD_BF16 / GMD_F16 are implemented (float32 composes gmd_gemm_nt twice and gmd_scaled_add)", fn);
         return GMD_ERR_UNSUPPORTED;
     }
-    GMD_REQUIRE(M >= 0 && K > 0 && N > 0, "gmd_lora_update: bad shape M=%d K=%d N=%d", M, K, N);
-    GMD_REQUIRE(K % 64 == 0, "gmd_lora_update: K=%d must be a multiple of 64", K);
-    GMD_REQUIRE(Rp > 0 && Rp % 32 == 0, "gmd_lora_update: padded rank Rp=%d must be a positive multiple of 32", Rp);
-    GMD_REQUIRE(Rp <= 128, "gmd_lora_update: padded rank Rp=%d above 128", Rp);
-    GMD_REQUIRE(scales != nullptr && index >= 0, "gmd_lora_update: scales must be a device array, the index non-negative");
+    GMD_REQUIRE(M >= 0 && K > 0 && N > 0, "%s: bad shape M=%d K=%d N=%d", fn, M, K, N);
+    GMD_REQUIRE(K % 64 == 0, "%s: K=%d must be a multiple of 64", fn, K);
+    if (int rc = check_rank_and_table(fn, Rp, sa)) return rc;
     if (transposed) {
-        GMD_REQUIRE(batch > 0 && tokens > 0 && (int64_t)batch * tokens == M, "gmd_lora_update: transposed mode needs M=%d == batch=%d * tokens=%d",
+        GMD_REQUIRE(batch > 0 && tokens > 0 && (int64_t)batch * tokens == M, "%s: transposed mode needs M=%d == batch=%d * tokens=%d", fn,
                     M, batch, tokens);
-        GMD_REQUIRE(ldy >= ((int64_t)tokens + 7) / 8 * 8, "gmd_lora_update: ldy=%lld must cover tokens=%d rounded up to 8", (long long)ldy, tokens);
-        GMD_REQUIRE(strideY >= (int64_t)N * ldy && strideY % 8 == 0, "gmd_lora_update: strideY=%lld must cover N*ldy and be a multiple of 8",
+        GMD_REQUIRE(ldy >= ((int64_t)tokens + 7) / 8 * 8, "%s: ldy=%lld must cover tokens=%d rounded up to 8", fn, (long long)ldy, tokens);
+        GMD_REQUIRE(strideY >= (int64_t)N * ldy && strideY % 8 == 0, "%s: strideY=%lld must cover N*ldy and be a multiple of 8", fn,
                     (long long)strideY);
     } else {
-        GMD_REQUIRE(N % 8 == 0, "gmd_lora_update: N=%d must be a multiple of 8 (16-byte pieces of Y)", N);
-        GMD_REQUIRE(ldy >= N, "gmd_lora_update: ldy=%lld smaller than N=%d", (long long)ldy, N);
+        GMD_REQUIRE(N % 8 == 0, "%s: N=%d must be a multiple of 8 (16-byte pieces of Y)", fn, N);
+        GMD_REQUIRE(ldy >= N, "%s: ldy=%lld smaller than N=%d", fn, (long long)ldy, N);
     }
     if (M == 0) return GMD_OK;  // nothing to write
-    GMD_REQUIRE(X && Aw && Bw && Y, "gmd_lora_update: null pointer");
-    GMD_REQUIRE(gmd_aligned16(X) && gmd_aligned16(Aw) && gmd_aligned16(Bw) && gmd_aligned16(Y), "gmd_lora_update: pointers must be 16-byte aligned");
-    GMD_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "gmd_lora_update: leading dimensions must be multiples of 8");
-    GMD_REQUIRE(ldx >= K, "gmd_lora_update: ldx=%lld smaller than K=%d", (long long)ldx, K);
+    GMD_REQUIRE(X && Aw && Bw && Y, "%s: null pointer", fn);
+    GMD_REQUIRE(gmd_aligned16(X) && gmd_aligned16(Aw) && gmd_aligned16(Bw) && gmd_aligned16(Y), "%s: pointers must be 16-byte aligned", fn);
+    GMD_REQUIRE(ldx % 8 == 0 && ldy % 8 == 0, "%s: leading dimensions must be multiples of 8", fn);
+    GMD_REQUIRE(ldx >= K, "%s: ldx=%lld smaller than K=%d", fn, (long long)ldx, K);
     const int64_t xbytes = (((int64_t)M - 1) * ldx + K) * 2;
     const int64_t yslab = transposed ? (((int64_t)N - 1) * ldy + (tokens + 7) / 8 * 8) * 2 : (((int64_t)M - 1) * ldy + N) * 2;
     const int64_t ybytes = transposed ? ((int64_t)batch - 1) * strideY * 2 + yslab : yslab;
-    GMD_REQUIRE(xbytes < (1ll << 31) && yslab < (1ll << 31), "gmd_lora_update: X or a batch entry of Y exceeds 2 GiB (32-bit byte offsets)");
+    GMD_REQUIRE(xbytes < (1ll << 31) && yslab < (1ll << 31), "%s: X or a batch entry of Y exceeds 2 GiB (32-bit byte offsets)", fn);
     {
         const uintptr_t x0 = (uintptr_t)X, x1 = x0 + (uintptr_t)xbytes, y0 = (uintptr_t)Y, y1 = y0 + (uintptr_t)ybytes;
-        GMD_REQUIRE(x1 <= y0 || y1 <= x0, "gmd_lora_update: X overlaps Y");
+        GMD_REQUIRE(x1 <= y0 || y1 <= x0, "%s: X overlaps Y", fn);
     }
     LoraParams p;
     p.X = (const bf16_t*)X; p.Aw = (const bf16_t*)Aw; p.Bw = (const bf16_t*)Bw; p.Y = (bf16_t*)Y;
-    p.scale = scales + index;
+    p.scale = sa.entry();
     p.M = M; p.K = K; p.N = N;
     p.tokens = transposed ? tokens : M;
     p.tblocks = (p.tokens + ROWS - 1) / ROWS;
@@ -453,12 +502,45 @@ extern "C" int gmd_lora_update(const void* X, const void* Aw, const void* Bw, vo
     p.F = nullptr; p.ldf = 0; p.fbytes = 0;
     p.xbytes = (unsigned)xbytes; p.ybytes = (unsigned)yslab;
     const int64_t gx = transposed ? (int64_t)batch * p.tblocks : ((int64_t)M + ROWS - 1) / ROWS;
-    GMD_REQUIRE(gx < (1ll << 31), "gmd_lora_update: grid too large");
+    GMD_REQUIRE(gx < (1ll << 31), "%s: grid too large", fn);
     const int ntiles = (N + NT - 1) / NT;
     p.tiles_per_y = tiles_per_y(gx, ntiles);
     dim3 grid((unsigned)gx, (unsigned)((ntiles + p.tiles_per_y - 1) / p.tiles_per_y), 1);
     hipStream_t s = (hipStream_t)stream;
-    return dtype == GMD_F16 ? dispatch_lora<f16_t>(p, Rp, transposed != 0, grid, s) : dispatch_lora<bf16_t>(p, Rp, transposed != 0, grid, s);
+    const int mode = transposed ? MODE_TRANS : MODE_PLAIN;
+    if (sa.stacked()) dtype == GMD_F16 ? dispatch_lora_stacked<f16_t>(p, Rp, mode, grid, s) : dispatch_lora_stacked<bf16_t>(p, Rp, mode, grid, s);
+    else dtype == GMD_F16 ? dispatch_lora<f16_t>(p, Rp, mode, grid, s) : dispatch_lora<bf16_t>(p, Rp, mode, grid, s);
+    GMD_CHECK_LAUNCH(fn);
+    return GMD_OK;
+}
+
+}  // namespace
+
+extern "C" int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                              int64_t ldx, int64_t ldy, int64_t ldf, const float* scales, int index, gmd_stream_t stream) {
+    return lora_geglu_impl("gmd_lora_geglu", X, Aw, Bw, Y, F, dtype, M, C, Rp, ldx, ldy, ldf, ScaleArg{scales, index, -1}, stream);
+}
+
+extern "C" int gmd_lora_geglu_stacked(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                                      int64_t ldx, int64_t ldy, int64_t ldf, const float* colscales, int index, int64_t ldc,
+                                      gmd_stream_t stream) {
+    GMD_REQUIRE(ldc >= 0, "gmd_lora_geglu_stacked: ldc=%lld smaller than Rp=%d", (long long)ldc, Rp);
+    return lora_geglu_impl("gmd_lora_geglu_stacked", X, Aw, Bw, Y, F, dtype, M, C, Rp, ldx, ldy, ldf, ScaleArg{colscales, index, ldc}, stream);
+}
+
+extern "C" int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N, int64_t ldx,
+                               int64_t ldy, int transposed, int batch, int tokens, int64_t strideY, const float* scales, int index,
+                               gmd_stream_t stream) {
+    return lora_update_impl("gmd_lora_update", X, Aw, Bw, Y, dtype, M, K, Rp, N, ldx, ldy, transposed, batch, tokens, strideY,
+                            ScaleArg{scales, index, -1}, stream);
+}
+
+extern "C" int gmd_lora_update_stacked(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N,
+                                       int64_t ldx, int64_t ldy, int transposed, int batch, int tokens, int64_t strideY,
+                                       const float* colscales, int index, int64_t ldc, gmd_stream_t stream) {
+    GMD_REQUIRE(ldc >= 0, "gmd_lora_update_stacked: ldc=%lld smaller than Rp=%d", (long long)ldc, Rp);
+    return lora_update_impl("gmd_lora_update_stacked", X, Aw, Bw, Y, dtype, M, K, Rp, N, ldx, ldy, transposed, batch, tokens, strideY,
+                            ScaleArg{colscales, index, ldc}, stream);
 }
 
 GMD_WG_TRACE_SETTER(lora)

@@ -95,6 +95,8 @@ SIGNATURES = {
     "gmd_scaled_add": [P, P, P, I, L, P, I, P],
     "gmd_lora_update": [P, P, P, P, I, I, I, I, I, L, L, I, I, I, L, P, I, P],
     "gmd_lora_geglu": [P, P, P, P, P, I, I, I, I, L, L, L, P, I, P],
+    "gmd_lora_update_stacked": [P, P, P, P, I, I, I, I, I, L, L, I, I, I, L, P, I, L, P],
+    "gmd_lora_geglu_stacked": [P, P, P, P, P, I, I, I, I, L, L, L, P, I, L, P],
     "gmd_cast": [P, I, P, I, L, P],
     "gmd_dup_batch": [P, P, L, P],
 }

@@ -45,6 +45,19 @@ _PARTS = ((".lora_A.weight", _DOWN), (".lora_B.weight", _UP), (".lora.down.weigh
 _PROCESSOR = re.compile(r"^(.*)\.processor\.(to_q|to_k|to_v|to_out)_lora\.(down|up)\.weight$")
 
 
+class LoraAdapterError(ValueError, NotImplementedError):
+    """A call names an adapter that cannot be addressed: a name or an adapter that is already loaded, a name that is not loaded, a
+    state dict without factors.  A ``ValueError`` -- the arguments are wrong -- that is ALSO a ``NotImplementedError``: while one
+    adapter at a time was implemented, ``set_adapters``, ``adapter_name=`` and a second ``load_lora`` raised that, and callers that
+    catch it keep working (the idiom of ``io.UnsupportedOperation``, an ``OSError`` and a ``ValueError``)."""
+
+
+def same_adapter(p, q):
+    """Do two parsed adapters ({module: (A, B, alpha)}) hold the same factors on the same modules?"""
+    return p.keys() == q.keys() and all(p[m][2] == q[m][2] and p[m][0].shape == q[m][0].shape and torch.equal(p[m][0], q[m][0])
+                                        and torch.equal(p[m][1], q[m][1]) for m in p)
+
+
 def _check_targets(targets):
     if targets not in TARGETS:
         raise ValueError(f"LoRA: targets={targets!r} is not one of {TARGETS}")
@@ -172,6 +185,96 @@ def parse_lora_state_dict(sd, module_names, ignore_unsupported=False, targets="a
 def factor(rank, alpha):
     """The adapter's own factor alpha / r (1 without an alpha)."""
     return 1.0 if alpha is None else float(alpha) / rank
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# several adapters at once: the host-side packing (pure CPU: tests/test_lora_multi_cpu.py)
+# ---------------------------------------------------------------------------------------------------------------------------
+class ModulePacking:
+    """One adapted module: ``adapters`` (load order), their ``ranks``, the column ``ranges`` [c0, c1) of each in the tightly packed
+    stack, ``rank`` (the sum), ``padded`` (the sum rounded up to the multiple), ``slots`` (each adapter's entry in the table of scalar
+    scales) and ``row`` (the module's row in the table of column scales; None for a module with ONE adapter, which keeps the
+    single-adapter launch)."""
+
+    def __init__(self, adapters, ranks, ranges, padded, slots, row):
+        self.adapters, self.ranks, self.ranges, self.padded, self.slots, self.row = adapters, ranks, ranges, padded, slots, row
+        self.rank = sum(ranks)
+
+    @property
+    def stacked(self):
+        return self.row is not None
+
+
+class Packing:
+    """``modules``: {module: ModulePacking} in sorted module order; ``slots``: [(module, adapter)] -- one scalar scale each, sorted by
+    module, then load order (ONE adapter: slot i is module i, today's table); ``rows`` / ``width``: the table of column scales holds
+    one row per stacked module, ``width`` = the largest padded stacked rank."""
+
+    def __init__(self, modules, slots, rows, width):
+        self.modules, self.slots, self.rows, self.width = modules, slots, rows, width
+
+
+def pack_adapters(adapters, multiple=32, limit=None):
+    """``adapters``: {adapter name: {module: (A [r, K], B [N, r], alpha or None)}} in LOAD order (``parse_lora_state_dict`` each).
+    Returns the ``Packing``: a module targeted by one adapter keeps its single launch; a module targeted by two or more gets their
+    factors packed tightly along the rank, in load order, and the padding (to ``multiple``) applies to the SUM.  A padded sum above
+    ``limit`` (default: the stacked kernel's 256) raises ``NotImplementedError`` naming the module, the ranks and the limit."""
+    from ..hip_ops import LORA_MAX_STACKED_RANK
+
+    limit = LORA_MAX_STACKED_RANK if limit is None else limit
+    names = sorted({m for parsed in adapters.values() for m in parsed})
+    modules, slots, rows, width = {}, [], 0, 0
+    for m in names:
+        who = [n for n, parsed in adapters.items() if m in parsed]
+        ranks = [adapters[n][m][0].shape[0] for n in who]
+        padded = -(-sum(ranks) // multiple) * multiple
+        if len(who) > 1 and padded > limit:
+            raise NotImplementedError(f"LoRA: module {m}: the ranks {' + '.join(str(r) for r in ranks)} of adapters {who} sum to {sum(ranks)} "
+                                      f"(padded {padded}), above the stacked kernel's limit of {limit}")
+        ranges, c = [], 0
+        for r in ranks:
+            ranges.append((c, c + r))
+            c += r
+        row = None
+        if len(who) > 1:
+            row, rows, width = rows, rows + 1, max(width, padded)
+        modules[m] = ModulePacking(who, ranks, ranges, padded, list(range(len(slots), len(slots) + len(who))), row)
+        slots.extend((m, n) for n in who)
+    return Packing(modules, slots, rows, width)
+
+
+def stack_factors(adapters, module, mp):
+    """The stacked factors of ``module`` (``mp``: its ModulePacking): (A [padded, K], B [N, padded]) float32, adapter a at columns
+    ``mp.ranges[a]``, zeros beyond the sum."""
+    a0, b0, _ = adapters[mp.adapters[0]][module]
+    a, b = torch.zeros(mp.padded, a0.shape[1]), torch.zeros(b0.shape[0], mp.padded)
+    for n, (c0, c1) in zip(mp.adapters, mp.ranges):
+        a[c0:c1], b[:, c0:c1] = adapters[n][module][0], adapters[n][module][1]
+    return a, b
+
+
+def scale_tables(adapters, packing, weights, scale=1.0):
+    """The two float32 tables the kernels read: ``scalars`` [len(slots)], entry (module, a) = scale * weights[a] * alpha_a / r_a, and
+    ``columns`` [rows, width] (at least [1, 1]), the row of a stacked module holding that very number on adapter a's columns and 0 on
+    the pad columns.  An adapter missing from ``weights`` has weight 0.  Each entry is float32(alpha / r) * float32(scale * weight),
+    one float32 product: with weight 1 the very number the single-adapter table has always held."""
+    def f32(values):
+        return torch.tensor(values, dtype=torch.float32)
+
+    def sw(n):
+        return float(scale) * float(weights.get(n, 0.0))
+
+    def fac(m, n):
+        a, _, alpha = adapters[n][m]
+        return factor(a.shape[0], alpha)
+
+    scalars = f32([fac(m, n) for m, n in packing.slots]) * f32([sw(n) for _, n in packing.slots])
+    columns = torch.zeros(max(packing.rows, 1), max(packing.width, 1), dtype=torch.float32)
+    for m, mp in packing.modules.items():
+        if mp.stacked:
+            for n, (c0, c1) in zip(mp.adapters, mp.ranges):
+                columns[mp.row, c0:c1] = f32([fac(m, n)]) * f32([sw(n)])
+    return scalars, columns
 
 
 def load_lora_file(path_or_state_dict, weight_name=None, subfolder=None):

@@ -249,12 +249,30 @@ def _lora_key(model):
     return None if getattr(model, "_lora_raw", None) is None else (model._lora_id, model._lora_version)
 
 
+class _LoraStack:
+    """A projection targeted by two or more adapters: the stacked factors ``a`` [Rp, K] / ``b`` [N, Rp] and the module's ``row`` in the
+    table of column scales (the one stacked launch), or ``parts`` = [(a_i, b_i, slot_i)] in load order (the sequential route: float32,
+    GMD_LORA_STACK_FUSED=0).  Only the operands of the route the model takes are on the device."""
+
+    def __init__(self, a, b, row, parts):
+        self.a, self.b, self.row, self.parts = a, b, row, parts
+
+    def seq(self, scales):
+        return None if self.parts is None else [(a, b, scales, i) for a, b, i in self.parts]
+
+
 def _lora_apply(model, lr, proj, x, y, col=0, tokens=None, x_split=False):
-    """One ``hip_ops.lora_update`` behind an adapted projection (nothing when the adapter does not target ``proj`` of this block)."""
+    """ONE launch behind an adapted projection -- ``hip_ops.lora_update`` for a projection one adapter targets,
+    ``hip_ops.lora_update_stacked`` for one that several target (nothing when no adapter targets ``proj`` of this block)."""
     ent = lr.get(proj)
-    if ent is not None:
-        ops.lora_update(x, ent[0], ent[1], y, model._lora_w["scales"], ent[2], transposed=tokens is not None, tokens=tokens, col=col,
-                        x_split=x_split)
+    if ent is None:
+        return
+    lw = model._lora_w
+    if isinstance(ent, _LoraStack):
+        ops.lora_update_stacked(x, ent.a, ent.b, y, lw["colscales"], ent.row, transposed=tokens is not None, tokens=tokens, col=col,
+                                x_split=x_split, parts=ent.seq(lw["scales"]))
+    else:
+        ops.lora_update(x, ent[0], ent[1], y, lw["scales"], ent[2], transposed=tokens is not None, tokens=tokens, col=col, x_split=x_split)
 
 
 _LORA_IDS = [0]
@@ -318,12 +336,15 @@ class UNet2DConditionModel(_HipModule):
         self._ip_kv = {}          # ... persistent K_ip / V_ip^T per (layer, rows, Nip, dtype), rewritten in place by prepare_ip_context
         self._ip_scale = 1.0      # ... set_ip_adapter_scale
         self._ip_last = None      # ... (key of the embeddings, their context, the embeddings) of the latest prepare_ip_context
-        self._lora_raw = None     # LoRA: {module: (A [r, K], B [N, r], alpha or None)} CPU float32 (load_lora), None when no adapter is loaded
+        self._lora_adapters = {}  # LoRA: {adapter name: {module: (A [r, K], B [N, r], alpha or None)}} CPU float32, in load order (load_lora)
+        self._lora_weights = {}   # ... {adapter name: weight} (set_adapters; 1.0 at load)
+        self._lora_saved = None   # ... the weights disable_lora() remembered for enable_lora(), None when not disabled
+        self._lora_raw = None     # ... the same factors by module: {module: [(adapter, A, B, alpha), ...]}; None when no adapter is loaded
         self._lora_w = None       # ... the factors in kernel layouts + the device table of scales, built on first use (_ensure_lora)
         self._lora_w_of = None
         self._lora_scale = 1.0    # ... set_lora_scale
-        self._lora_id = 0         # ... identity of the loaded adapter (graph key, cross-attention K / V cache key)
-        self._lora_version = 0    # ... bumped by load_lora / unload_lora / set_lora_scale: cached cross-attention K / V hold the scale
+        self._lora_id = 0         # ... identity of the loaded SET of adapters (graph key, cross-attention K / V cache key)
+        self._lora_version = 0    # ... bumped by whatever changes the update (adapters, weights, scale): cached cross-attention K / V hold it
         self._freeu = None        # FreeU: (s1, s2, b1, b2) of enable_freeu, None when off
         self._freeu_dev = None    # ... the same four numbers as the float32 device table the kernel reads, built on first use
 
@@ -927,43 +948,89 @@ class UNet2DConditionModel(_HipModule):
         return ent["kc"], ent["vt"], self._ip_w["layers"][t["key"]]["index"]
 
     # ------------------------------------------------------------------------------------------
-    # LoRA: one adapter, kept in factors and applied at run time (hip_ops.lora_update); components/lora.py reads the checkpoints
+    # LoRA: adapters kept in factors and applied at run time (hip_ops.lora_update; several on one projection: lora_update_stacked);
+    # components/lora.py reads the checkpoints and packs the stacks
     # ------------------------------------------------------------------------------------------
     def lora_module_names(self):
         """The model's own module names, the table kohya's flattened names are resolved against."""
         return [k[: -len(".weight")] for k in self.expected_keys() if k.endswith(".weight")]
 
-    def load_lora(self, state_dict, ignore_unsupported=False, targets="attention"):
-        """Load ONE LoRA adapter (PEFT / diffusers / kohya keys: components/lora.py) for the attention projections of the transformer
+    def load_lora(self, state_dict, ignore_unsupported=False, targets="attention", adapter_name=None):
+        """Load a LoRA adapter (PEFT / diffusers / kohya keys: components/lora.py) for the attention projections of the transformer
         blocks; ``targets="transformer"`` also takes the feed-forward's ``ff.net.0.proj`` / ``ff.net.2`` and the transformers'
         ``proj_in`` / ``proj_out``.  Host work only: the factors go to the device, in the model's dtype and beside the prepared weights,
         at first use.  No weight buffer changes: every targeted projection is followed by one ``hip_ops.lora_update`` (``ff.net.0.proj``:
-        by ``hip_ops.lora_geglu``, the update and the GEGLU in one launch; a block with a feed-forward target leaves ff_geglu_fused)."""
+        by ``hip_ops.lora_geglu``, the update and the GEGLU in one launch; a block with a feed-forward target leaves ff_geglu_fused).
+
+        May be called repeatedly: each call adds one adapter under ``adapter_name`` (default ``default_0``, ``default_1``, ... as in
+        diffusers; a name already loaded is a ``ValueError``) with weight 1.0; ``targets`` / ``ignore_unsupported`` are per adapter.
+        The SAME adapter a second time (equal factors on the same modules, under whatever name) is refused as already loaded -- it
+        would silently double its effect, which ``set_adapters(name, 2.0)`` says in the open.  Both refusals, an unknown name and a
+        state dict without factors raise ``lora.LoraAdapterError``, a ``ValueError`` that is also a ``NotImplementedError``.  A
+        projection that two or more adapters target still takes ONE launch (``hip_ops.lora_update_stacked``: the factors side by side
+        along the rank, a scale per rank column); each adapter's own rank stays <= 128, and ranks on one module that sum, after padding,
+        to more than 256 raise ``NotImplementedError`` (naming the module, the ranks and the limit) and leave the model as it was."""
         from . import lora as _lora
 
-        if self._lora_raw is not None:
-            raise NotImplementedError("load_lora: an adapter is already loaded and several adapters at once are not implemented "
-                                      "(unload_lora() first)")
+        if self._capturing:
+            raise HipExtensionError("a LoRA adapter must be loaded outside graph capture")
+        if adapter_name is None:
+            i = len(self._lora_adapters)
+            while f"default_{i}" in self._lora_adapters:
+                i += 1
+            adapter_name = f"default_{i}"
+        if not isinstance(adapter_name, str) or not adapter_name:
+            raise ValueError(f"load_lora: adapter_name={adapter_name!r} must be a non-empty string")
+        if adapter_name in self._lora_adapters:
+            raise _lora.LoraAdapterError(f"load_lora: an adapter named {adapter_name!r} is already loaded (delete_adapters({adapter_name!r}) "
+                                         "first)")
         parsed = _lora.parse_lora_state_dict(state_dict, self.lora_module_names(), ignore_unsupported=ignore_unsupported,
                                              targets=targets)
         if not parsed:
-            raise ValueError("load_lora: the state dict holds no LoRA factors for this UNet's attention projections"
-                             + (", feed-forwards or proj_in / proj_out" if targets == "transformer" else ""))
+            raise _lora.LoraAdapterError("load_lora: the state dict holds no LoRA factors for this UNet's attention projections"
+                                         + (", feed-forwards or proj_in / proj_out" if targets == "transformer" else ""))
+        for other, loaded in self._lora_adapters.items():
+            if _lora.same_adapter(parsed, loaded):
+                raise _lora.LoraAdapterError(f"load_lora: this adapter is already loaded as {other!r} (the same factors on the same modules); "
+                                             f"loading it twice is not implemented -- set_adapters({other!r}, 2.0) doubles its weight")
         shapes = self.expected_keys()
         for name, (a, b, _) in parsed.items():
             n, k = shapes[name + ".weight"][:2]
             if a.shape[1] != k or b.shape[0] != n:
                 raise ValueError(f"load_lora: {name}: factors {tuple(b.shape)} x {tuple(a.shape)} do not fit the [{n}, {k}] projection")
-        _LORA_IDS[0] += 1
-        self._lora_raw, self._lora_id, self._lora_scale = parsed, _LORA_IDS[0], 1.0
-        self._drop_lora_device_state()
+        adapters = dict(self._lora_adapters)
+        adapters[adapter_name] = parsed
+        _lora.pack_adapters(adapters)  # the stacked ranks must fit: raises before anything of the model has changed
+        if not self._lora_adapters:
+            self._lora_scale = 1.0
+        self._lora_weights[adapter_name] = 0.0 if self._lora_saved is not None else 1.0
+        if self._lora_saved is not None:
+            self._lora_saved[adapter_name] = 1.0
+        self._set_lora_adapters(adapters)
         return self
 
-    def unload_lora(self):
-        """Back to the UNet without an adapter: the launches, and so the outputs, of a model that never had one."""
-        self._lora_raw = None
-        self._lora_scale = 1.0
+    def _set_lora_adapters(self, adapters):
+        """A new SET of adapters: layouts and launches change, so the device state and the ("lora",)-keyed graphs go."""
+        self._lora_adapters = adapters
+        self._lora_weights = {n: self._lora_weights[n] for n in adapters}
+        if adapters:
+            raw = {}
+            for n, parsed in adapters.items():
+                for m, (a, b, alpha) in parsed.items():
+                    raw.setdefault(m, []).append((n, a, b, alpha))
+            self._lora_raw = {m: raw[m] for m in sorted(raw)}
+        else:
+            self._lora_raw, self._lora_scale, self._lora_saved = None, 1.0, None
+        _LORA_IDS[0] += 1
+        self._lora_id = _LORA_IDS[0]
         self._drop_lora_device_state()
+
+    def unload_lora(self):
+        """Back to the UNet without an adapter (ALL adapters go): the launches, and so the outputs, of a model that never had one."""
+        if self._capturing:
+            raise HipExtensionError("LoRA adapters must be unloaded outside graph capture")
+        self._lora_weights = {}
+        self._set_lora_adapters({})
         return self
 
     def _drop_lora_device_state(self):
@@ -975,21 +1042,101 @@ class UNet2DConditionModel(_HipModule):
     def has_lora(self):
         return self._lora_raw is not None
 
+    def list_adapters(self):
+        """The names of the loaded adapters, in load order."""
+        return list(self._lora_adapters)
+
+    def active_adapters(self):
+        """The loaded adapters whose weight is not 0, in load order (none while ``disable_lora()`` holds)."""
+        return [n for n in self._lora_adapters if self._lora_weights[n] != 0.0]
+
+    def _known_adapters(self, what, names):
+        from . import lora as _lora
+
+        names = [names] if isinstance(names, str) else list(names)
+        unknown = [n for n in names if n not in self._lora_adapters]
+        if unknown:
+            raise _lora.LoraAdapterError(f"{what}: no adapter named {unknown} is loaded (loaded: {self.list_adapters()})")
+        if len(set(names)) != len(names):
+            raise ValueError(f"{what}: a name is given twice in {names}")
+        return names
+
+    def set_adapters(self, names, weights=None):
+        """diffusers' ``set_adapters``: ``names`` (one name or a list) become the active adapters with ``weights`` (one float per name,
+        default 1.0); every other loaded adapter gets weight 0 -- its launches stay, its columns contribute nothing.  Unknown names are
+        a ``ValueError``; per-block weight dicts (diffusers' ``{"down": ..., "mid": ..., "up": ...}``) are not implemented and refused
+        by name.  Only the float32 device tables change (outside any graph capture): every captured graph is kept; the cross-attention
+        K / V^T, cached WITH the update, are recomputed at the next ``update_context``."""
+        names = self._known_adapters("set_adapters", names)
+        if isinstance(weights, dict) or (isinstance(weights, (list, tuple)) and any(isinstance(w, dict) for w in weights)):
+            raise NotImplementedError("set_adapters: per-block adapter weights (a dict per adapter) are not implemented: one float per adapter")
+        if weights is None:
+            weights = [1.0] * len(names)
+        elif not isinstance(weights, (list, tuple)):
+            weights = [weights] * len(names)
+        if len(weights) != len(names):
+            raise ValueError(f"set_adapters: {len(weights)} weights for {len(names)} adapters")
+        weights = [1.0 if w is None else float(w) for w in weights]
+        if not all(math.isfinite(w) for w in weights):
+            raise ValueError(f"set_adapters: weights {weights} must be finite")
+        new = {n: 0.0 for n in self._lora_adapters}
+        new.update(zip(names, weights))
+        self._lora_saved = None
+        self._write_lora_tables(new, self._lora_scale)
+
+    def delete_adapters(self, names):
+        """Drop the named adapters (unknown names: ``ValueError``); the others keep their weights.  Layouts and launches change as at a
+        load; a model brought back to ONE adapter launches and computes exactly what a model that only ever loaded that one does."""
+        names = self._known_adapters("delete_adapters", names)
+        if self._capturing:
+            raise HipExtensionError("LoRA adapters must be deleted outside graph capture")
+        if self._lora_saved is not None:
+            self._lora_saved = {n: w for n, w in self._lora_saved.items() if n not in names}
+        self._set_lora_adapters({n: p for n, p in self._lora_adapters.items() if n not in names})
+        return self
+
+    def disable_lora(self):
+        """Every adapter weight to 0, remembered for ``enable_lora()``.  The LAUNCHES STAY -- each adds exactly 0 where its scale is 0
+        -- so no graph is dropped and the result is that of the UNet without an adapter up to the roundings the feed-forward route of
+        an adapted block differs by (an adapted block leaves ff_geglu_fused); ``unload_lora()`` gives the launches of a model that
+        never had an adapter."""
+        if self._lora_raw is None:
+            raise ValueError("disable_lora: no LoRA adapter is loaded")
+        if self._lora_saved is None:
+            saved = dict(self._lora_weights)
+            self._write_lora_tables({n: 0.0 for n in self._lora_adapters}, self._lora_scale)
+            self._lora_saved = saved
+
+    def enable_lora(self):
+        """The weights ``disable_lora()`` remembered, back in the tables (nothing when it was not called)."""
+        if self._lora_raw is None:
+            raise ValueError("enable_lora: no LoRA adapter is loaded")
+        if self._lora_saved is not None:
+            saved, self._lora_saved = self._lora_saved, None
+            self._write_lora_tables(saved, self._lora_scale)
+
     def set_lora_scale(self, scale):
-        """The adapter's scale (diffusers' ``cross_attention_kwargs={"scale": s}``; default 1.0): ``scales[i] = s * alpha_i / r_i`` is
-        rewritten in the float32 device table the kernels read -- outside any captured graph, so a captured forward serves every scale.
-        The cross-attention K / V^T are cached per prompt WITH the update, so they are recomputed at the next ``update_context``."""
+        """The global LoRA scale (diffusers' ``cross_attention_kwargs={"scale": s}``; default 1.0), on top of the adapter weights: entry
+        (module, adapter a) of the float32 device tables the kernels read is ``s * w_a * alpha_a / r_a``, rewritten outside any captured
+        graph, so a captured forward serves every scale.  The cross-attention K / V^T are cached per prompt WITH the update, so they are
+        recomputed at the next ``update_context``."""
         if self._lora_raw is None:
             raise ValueError("set_lora_scale: no LoRA adapter is loaded")
+        self._write_lora_tables(self._lora_weights, float(scale))
+
+    def _write_lora_tables(self, weights, scale):
         if self._capturing:
-            raise HipExtensionError("the LoRA scale must be set outside graph capture")
-        scale = float(scale)
-        if scale == self._lora_scale:
+            raise HipExtensionError("the LoRA scale and adapter weights must be set outside graph capture")
+        if scale == self._lora_scale and weights == self._lora_weights:
             return
-        self._lora_scale = scale
+        self._lora_weights, self._lora_scale = dict(weights), scale
         self._lora_version += 1
         if self._lora_w is not None and self._lora_w_of is self._w:
-            self._lora_w["scales"].copy_(self._lora_w["factors"] * scale)
+            from . import lora as _lora
+
+            scalars, columns = _lora.scale_tables(self._lora_adapters, self._lora_w["packing"], self._lora_weights, self._lora_scale)
+            self._lora_w["scales"].copy_(scalars)
+            self._lora_w["colscales"].copy_(columns)
 
     # ------------------------------------------------------------------------------------------
     # FreeU: diffusers' UNet2DConditionModel.enable_freeu / disable_freeu (hip_ops.concat_channels_freeu in up blocks 0 and 1)
@@ -1048,9 +1195,11 @@ class UNet2DConditionModel(_HipModule):
         return self._freeu_dev
 
     def _ensure_lora(self):
-        """The adapter's factors in kernel layouts, next to (and for) the prepared UNet weights: the rank zero-padded to the multiple
+        """The adapters' factors in kernel layouts, next to (and for) the prepared UNet weights: the rank zero-padded to the multiple
         the contractions of this dtype mode need, ``a`` a W operand (pre-split where the weights are), ``b`` a W operand for the plain
-        outputs and an A operand for the V^T outputs (as the model's own to_v weights)."""
+        outputs and an A operand for the V^T outputs (as the model's own to_v weights).  A module one adapter targets: (a, b, slot in
+        the table of scalar scales).  A module several target: a ``_LoraStack`` -- the stacked factors and the row of column scales
+        in the 16-bit types, the adapters one by one where the sequential route runs (float32, GMD_LORA_STACK_FUSED=0)."""
         self._ensure()
         if self._lora_w is not None and self._lora_w_of is self._w:
             return self._lora_w
@@ -1059,27 +1208,44 @@ class UNet2DConditionModel(_HipModule):
         from . import lora as _lora
 
         mult = ops.lora_rank_multiple(self._dtype, split=self._split_mode())
-        layers, factors = {}, []
-        for i, name in enumerate(sorted(self._lora_raw)):
-            a, b, alpha = self._lora_raw[name]
-            r = a.shape[0]
-            rp = _pad_to(r, mult)
-            ap, bp = torch.zeros(rp, a.shape[1]), torch.zeros(b.shape[0], rp)
-            ap[:r], bp[:, :r] = a, b
+        stack_fused = ops.is_half(self._dtype) and ops.USE_LORA_STACK_FUSED
+        packing = _lora.pack_adapters(self._lora_adapters)
+        layers = {}
+        for name, mp in packing.modules.items():
+            interleave = False
             if name.endswith(_lora.FF_SUFFIXES):
                 blk, proj = name.split(".ff.net.", 1)
                 proj = "ff.net." + proj
-                if proj == "ff.net.0.proj" and (ops.is_half(self._dtype) or self._split_mode()):
-                    bp = ops.geglu_interleave(bp)  # the row order of the block's ff1 weight (_prepare_encoder): y's columns arrive in it
+                # the row order of the block's ff1 weight (_prepare_encoder): y's columns arrive in it
+                interleave = proj == "ff.net.0.proj" and (ops.is_half(self._dtype) or self._split_mode())
             elif name.endswith(_lora.PROJ_SUFFIXES):
                 blk, proj = name.rsplit(".", 1)  # the Transformer2DModel itself
             else:
                 blk, proj = name.rsplit(".attn", 1)
                 proj = "attn" + proj
-            layers.setdefault(blk, {})[proj] = (self._wt(ap), self._wa(bp) if proj.endswith("to_v") else self._wt(bp), i)
-            factors.append(_lora.factor(r, alpha))
-        factors = torch.tensor(factors, dtype=torch.float32)
-        w = dict(layers=layers, factors=factors, scales=(factors * self._lora_scale).to(self._device))
+
+            def device_pair(ap, bp):
+                if interleave:
+                    bp = ops.geglu_interleave(bp)
+                return self._wt(ap), self._wa(bp) if proj.endswith("to_v") else self._wt(bp)
+
+            def padded_pair(n):
+                a, b, _ = self._lora_adapters[n][name]
+                r = a.shape[0]
+                rp = _pad_to(r, mult)
+                ap, bp = torch.zeros(rp, a.shape[1]), torch.zeros(b.shape[0], rp)
+                ap[:r], bp[:, :r] = a, b
+                return device_pair(ap, bp)
+
+            if not mp.stacked:
+                ent = padded_pair(mp.adapters[0]) + (mp.slots[0],)
+            elif stack_fused:
+                ent = _LoraStack(*device_pair(*_lora.stack_factors(self._lora_adapters, name, mp)), mp.row, None)
+            else:
+                ent = _LoraStack(None, None, mp.row, [padded_pair(n) + (i,) for n, i in zip(mp.adapters, mp.slots)])
+            layers.setdefault(blk, {})[proj] = ent
+        scalars, columns = _lora.scale_tables(self._lora_adapters, packing, self._lora_weights, self._lora_scale)
+        w = dict(layers=layers, packing=packing, scales=scalars.to(self._device), colscales=columns.to(self._device))
         self._lora_w, self._lora_w_of = w, self._w
         return w
 
@@ -1177,10 +1343,14 @@ class UNet2DConditionModel(_HipModule):
         e1 = lr.get("ff.net.0.proj")
         if e1 is not None:
             y = ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1])
-            if t["ff1_fused"]:  # interleaved ff1 rows (16-bit, float32 split): e1's b rows are permuted alike (_ensure_lora)
+            if not t["ff1_fused"]:  # float32 exact: [value half | gate half]
+                _lora_apply(self, lr, "ff.net.0.proj", n3, y)
+                f = ops.geglu(y)
+            elif isinstance(e1, _LoraStack):  # several adapters: still one launch for the update and the GEGLU
+                f = ops.lora_geglu_stacked(n3, e1.a, e1.b, y, self._lora_w["colscales"], e1.row, x_split=ops.is_asplit(n3),
+                                           parts=e1.seq(scales))
+            else:  # interleaved ff1 rows (16-bit, float32 split): e1's b rows are permuted alike (_ensure_lora)
                 f = ops.lora_geglu(n3, e1[0], e1[1], y, scales, e1[2], x_split=ops.is_asplit(n3))
-            else:  # float32 exact: [value half | gate half]
-                f = ops.geglu(ops.lora_update(n3, e1[0], e1[1], y, scales, e1[2]))
         elif t["ff1_fused"]:
             f = ops.gemm_nt(n3, t["ff1"][0], bias=t["ff1"][1], act=ops.ACT_GEGLU, split_out=self._sa(t["ff2"][0]))
         else:

@@ -1041,6 +1041,102 @@ def lora_geglu(x, a, b_interleaved, y, scales, index, fused=None, x_split=False)
     return f
 
 
+# SEVERAL adapters on one projection: their factors stacked along the rank and ONE launch with a per-column scale
+# (gmd_lora_update_stacked / gmd_lora_geglu_stacked).  GMD_LORA_STACK_FUSED=0 (read once) sends a stacked projection down the
+# comparison route instead -- one lora_update per adapter, in load order, each with its own scalar scale -- what float32 always runs
+# (there is no float32 stacked kernel): the A/B switch, and the yardstick of tools/bench_lora_multi.py.
+USE_LORA_STACK_FUSED = os.environ.get("GMD_LORA_STACK_FUSED", "1") != "0"
+LORA_MAX_STACKED_RANK = 256  # the stacked kernel's limit on the padded SUM of the ranks (components/lora.py refuses more at load)
+
+
+def _lora_stack_route(name, x, a, b, colscales, fused, parts):
+    """True: the one stacked launch; False: the sequential route over ``parts``.  A missing operand of the chosen route is an error."""
+    fused = (USE_LORA_STACK_FUSED if fused is None else bool(fused)) and is_half(x.dtype)
+    if fused:
+        if a is None or b is None or colscales is None:
+            raise HipExtensionError(f"{name}: the stacked launch needs the stacked factors a, b and the table of column scales")
+        if colscales.dtype != torch.float32 or colscales.dim() != 2 or not colscales.is_contiguous():
+            raise HipExtensionError(f"{name}: colscales must be a contiguous float32 [rows, ldc] device tensor")
+        if a.dim() != 2 or b.dim() != 2 or a.shape[0] != b.shape[1] or a.shape[1] != x.shape[1]:
+            raise HipExtensionError(f"{name}: operand shapes inconsistent: x {tuple(x.shape)}, a {tuple(a.shape)}, b {tuple(b.shape)}")
+        if a.shape[0] > LORA_MAX_STACKED_RANK:
+            raise HipExtensionError(f"{name}: padded stacked rank {a.shape[0]} above {LORA_MAX_STACKED_RANK}")
+        if colscales.shape[1] < a.shape[0]:
+            raise HipExtensionError(f"{name}: colscales rows of {colscales.shape[1]} columns are shorter than the padded rank {a.shape[0]}")
+    elif not parts:
+        raise HipExtensionError(f"{name}: the sequential route (float32, GMD_LORA_STACK_FUSED=0, fused=False) needs parts=[(a, b, scales, "
+                                "index), ...], the adapters one by one")
+    return fused
+
+
+def lora_update_stacked(x, a, b, y, colscales, index, transposed=False, tokens=None, fused=None, col=0, x_split=False, parts=None):
+    """``y += ((x @ a.T) * colscales[index, :Rp]) @ b.T`` in place, the column scale applied in float32 in front of the ONE rounding of
+    the intermediate; returns ``y``.  a: [Rp, K] and b: [N, Rp] hold several adapters' factors side by side along the rank, the SUM of
+    the ranks zero-padded to a multiple of 32, Rp <= ``LORA_MAX_STACKED_RANK``; ``colscales``: float32 device table [rows, ldc >= Rp]
+    read by the kernel, so one captured graph serves every weight setting.  x, y, ``transposed`` / ``tokens`` / ``col`` / ``x_split``
+    as ``lora_update``.  16-bit types: ONE launch (gmd_lora_update_stacked) that reads and writes y once.  ``parts``: the same adapters
+    one by one, ``[(a_i, b_i, scales, index_i), ...]`` in load order (each as ``lora_update`` takes them) -- the sequential route, one
+    ``lora_update`` each: what float32 always takes and what ``fused=False`` (default: USE_LORA_STACK_FUSED) selects; it rounds y
+    between the adapters, so the two routes agree within their bounds, not bit for bit."""
+    if not _lora_stack_route("lora_update_stacked", x, a, b, colscales, fused, parts):
+        for pa, pb, ps, pi in parts:
+            lora_update(x, pa, pb, y, ps, pi, transposed=transposed, tokens=tokens, col=col, x_split=x_split)
+        return y
+    _dev(x, a, b, y, colscales)
+    if not isinstance(index, int) or isinstance(index, bool) or not 0 <= index < colscales.shape[0]:
+        raise HipExtensionError(f"lora_update_stacked: row index {index!r} outside the table of {colscales.shape[0]} rows")
+    if not (x.dtype == a.dtype == b.dtype == y.dtype):
+        raise HipExtensionError(f"lora_update_stacked: dtype mismatch {x.dtype} / {a.dtype} / {b.dtype} / {y.dtype}")
+    M, K = x.shape
+    N, Rp = b.shape
+    if transposed:
+        if y.dim() != 3 or tokens is None or tokens <= 0 or y.shape[0] * tokens != M or y.shape[1] != N or y.shape[2] < tokens or col:
+            raise HipExtensionError(f"lora_update_stacked: transposed y {tuple(y.shape)} does not hold [M / tokens, N, >= tokens] for M={M}, "
+                                    f"N={N}, tokens={tokens}")
+        batch, ldy = y.shape[0], y.shape[2]
+    else:
+        if y.dim() != 2 or y.shape[0] != M or col < 0 or col + N > y.shape[1]:
+            raise HipExtensionError(f"lora_update_stacked: y {tuple(y.shape)} does not hold columns [{col}, {col + N}) of {M} rows")
+        batch, tokens, ldy = 1, M, y.shape[1]
+    tm, t0 = _timed("lora_update")
+    check(lib().gmd_lora_update_stacked(_ptr(x), _ptr(a), _ptr(b), y.data_ptr() + col * y.element_size(), dtype_code(x.dtype), M, K, Rp, N, K,
+                                        ldy, int(bool(transposed)), batch, tokens, N * ldy, _ptr(colscales), index, colscales.shape[1],
+                                        _stream()), "gmd_lora_update_stacked")
+    if tm:
+        tm.end("lora_update", 2.0 * M * Rp * (K + N), (M * K + 2 * M * N + Rp * (K + N)) * x.element_size(), t0)
+    return y
+
+
+def lora_geglu_stacked(x, a, b_interleaved, y, colscales, index, fused=None, x_split=False, parts=None):
+    """``lora_geglu`` for several adapters stacked along the rank (operands as ``lora_update_stacked``; ``b_interleaved`` [8C, Rp] with
+    its rows in the order of the interleaved ff1 weight): returns F [M, 4C].  16-bit types: ONE launch (gmd_lora_geglu_stacked), y read
+    once and left unchanged.  Sequential route (``parts``; float32, ``fused=False``): one ``lora_update`` per adapter IN PLACE on y, then
+    ``geglu_interleaved``."""
+    if not _lora_stack_route("lora_geglu_stacked", x, a, b_interleaved, colscales, fused, parts):
+        for pa, pb, ps, pi in parts:
+            lora_update(x, pa, pb, y, ps, pi, x_split=x_split)
+        return geglu_interleaved(y)
+    _dev(x, a, b_interleaved, y, colscales)
+    if not isinstance(index, int) or isinstance(index, bool) or not 0 <= index < colscales.shape[0]:
+        raise HipExtensionError(f"lora_geglu_stacked: row index {index!r} outside the table of {colscales.shape[0]} rows")
+    if not (x.dtype == a.dtype == b_interleaved.dtype == y.dtype):
+        raise HipExtensionError(f"lora_geglu_stacked: dtype mismatch {x.dtype} / {a.dtype} / {b_interleaved.dtype} / {y.dtype}")
+    M, C = x.shape
+    Rp = a.shape[0]
+    if y.dim() != 2 or tuple(b_interleaved.shape) != (8 * C, Rp) or tuple(y.shape) != (M, 8 * C):
+        raise HipExtensionError(f"lora_geglu_stacked: operand shapes inconsistent: x {tuple(x.shape)}, a {tuple(a.shape)}, b "
+                                f"{tuple(b_interleaved.shape)}, y {tuple(y.shape)} (b must be [8C, Rp], y [M, 8C])")
+    if is_asplit(y) or not (x.is_contiguous() and y.is_contiguous()):
+        raise HipExtensionError("lora_geglu_stacked: x and y must be contiguous, y no pre-split activation")
+    f = torch.empty((M, 4 * C), dtype=x.dtype, device=x.device)
+    tm, t0 = _timed("lora_geglu")
+    check(lib().gmd_lora_geglu_stacked(_ptr(x), _ptr(a), _ptr(b_interleaved), _ptr(y), _ptr(f), dtype_code(x.dtype), M, C, Rp, C, 8 * C, 4 * C,
+                                       _ptr(colscales), index, colscales.shape[1], _stream()), "gmd_lora_geglu_stacked")
+    if tm:
+        tm.end("lora_geglu", 2.0 * M * Rp * 9 * C, (M * 13 * C + Rp * 9 * C) * x.element_size(), t0)
+    return f
+
+
 def softmax_rows(s, cols, scale, out_dtype, ldp=None, causal_nq=0):
     _dev(s)
     _f32(s, "softmax_rows input")

@@ -38,9 +38,10 @@ Behaviour notes kept from the reference: the latent channel count is forced to 4
 size is taken from ``sdr_latent`` (:1003-1015, ``height``/``width`` are ignored); unknown
 ``**kwargs`` are ignored (callers pass ``noise_level=``); per-call state lives on ``self``
 (not re-entrant).  The textual-inversion / IP-adapter mixins of the diffusers base are not part
-of this path (``ip_adapter_*`` raise ``NotImplementedError``).  LoRA: ``load_lora_weights`` loads ONE
-adapter from a local file, kept in factors and applied at run time (hip_ops.lora_update);
-``cross_attention_kwargs['scale']`` is its weight for the call (nothing without an adapter).
+of this path (``ip_adapter_*`` raise ``NotImplementedError``).  LoRA: ``load_lora_weights`` loads named
+adapters from local files, kept in factors and applied at run time (hip_ops.lora_update; several on one
+projection: hip_ops.lora_update_stacked), ``set_adapters`` weighs them;
+``cross_attention_kwargs['scale']`` is the scale of the call on top (nothing without an adapter).
 """
 from __future__ import annotations
 
@@ -129,7 +130,7 @@ class _GMPipelineBase(DiffusionPipeline):
         """diffusers' ``disable_freeu``: ``self.unet`` back to the launches of a model that never had FreeU."""
         self.unet.disable_freeu()
 
-    # ---- LoRA (diffusers' StableDiffusionLoraLoaderMixin, for LOCAL files; one adapter, kept in factors) ---------------------------
+    # ---- LoRA (diffusers' StableDiffusionLoraLoaderMixin, for LOCAL files; named adapters, kept in factors) -------------------------
     def load_lora_weights(self, path_or_state_dict, weight_name=None, subfolder=None, ignore_unsupported=False, adapter_name=None,
                           targets="attention", **kwargs):
         """diffusers' ``load_lora_weights`` for LOCAL files: a ``.safetensors`` file, a ``.bin`` / ``.pt`` torch pickle (read with
@@ -138,18 +139,17 @@ class _GMPipelineBase(DiffusionPipeline):
         ``self.unet`` (the dual pipeline: the SDR UNet; ``pipe.gm_unet.load_lora(...)`` adapts the GM UNet) and is applied at run
         time by one fused launch per targeted projection; targets that are not built raise unless ``ignore_unsupported``.
         ``targets``: "attention" (default: the eight attention projections of each transformer block) or "transformer" (also
-        ff.net.0.proj, ff.net.2, proj_in and proj_out: kohya's default target set)."""
+        ff.net.0.proj, ff.net.2, proj_in and proj_out: kohya's default target set).  May be called repeatedly: each call adds one
+        adapter under ``adapter_name`` (default ``default_0``, ``default_1``, ...); ``set_adapters`` weighs them."""
         from ..components import lora as _lora
 
-        if adapter_name is not None:
-            raise NotImplementedError("load_lora_weights(adapter_name=...): one adapter at a time is implemented, kept in factors and "
-                                      "applied at run time; there are no named adapters to switch between")
         if kwargs:
             raise NotImplementedError(f"load_lora_weights: unsupported arguments {sorted(kwargs)} (local files only)")
         self.unet.load_lora(_lora.load_lora_file(path_or_state_dict, weight_name=weight_name, subfolder=subfolder),
-                            ignore_unsupported=ignore_unsupported, targets=targets)
+                            ignore_unsupported=ignore_unsupported, targets=targets, adapter_name=adapter_name)
 
     def unload_lora_weights(self):
+        """Drops ALL adapters of ``self.unet``."""
         self.unet.unload_lora()
 
     def fuse_lora(self, *args, **kwargs):
@@ -159,9 +159,79 @@ class _GMPipelineBase(DiffusionPipeline):
 
     unfuse_lora = fuse_lora
 
-    def set_adapters(self, *args, **kwargs):
-        raise NotImplementedError("set_adapters: one adapter at a time is implemented (unload_lora_weights() and load another); "
-                                  "cross_attention_kwargs={'scale': s} sets its weight per call")
+    def _lora_unets(self):
+        """(component name, UNet) of every UNet that carries an adapter: ``unet``, and ``gm_unet`` where the pipeline has one."""
+        out = []
+        for name in ("unet", "gm_unet"):
+            u = getattr(self, name, None)
+            if u is not None and getattr(u, "has_lora", False):
+                out.append((name, u))
+        return out
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """diffusers' ``set_adapters``: the named adapters become active with ``adapter_weights`` (one float per name, default 1.0),
+        every other loaded adapter gets weight 0.  Each UNet is addressed only for the names IT has loaded (the dual pipeline: an
+        adapter loaded through ``pipe.gm_unet.load_lora`` is weighed by the same call); a name no UNet has loaded is a ``ValueError``
+        (``components.lora.LoraAdapterError``: also the ``NotImplementedError`` this method raised while one adapter was all there was).
+        Device tables only: no graph is captured anew.  ``cross_attention_kwargs={"scale": s}`` keeps its per-call meaning on top."""
+        from ..components import lora as _lora
+
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if isinstance(adapter_weights, dict) or (isinstance(adapter_weights, (list, tuple)) and any(isinstance(w, dict) for w in adapter_weights)):
+            raise NotImplementedError("set_adapters: per-block adapter weights (a dict per adapter) are not implemented: one float per adapter")
+        if adapter_weights is None or not isinstance(adapter_weights, (list, tuple)):
+            adapter_weights = [adapter_weights] * len(names)
+        if len(adapter_weights) != len(names):
+            raise ValueError(f"set_adapters: {len(adapter_weights)} weights for {len(names)} adapters")
+        unets = self._lora_unets()
+        loaded = {n for _, u in unets for n in u.list_adapters()}
+        unknown = [n for n in names if n not in loaded]
+        if unknown:
+            raise _lora.LoraAdapterError(f"set_adapters: no adapter named {unknown} is loaded (loaded: {self.get_list_adapters()})")
+        for _, u in unets:
+            mine = [(n, w) for n, w in zip(names, adapter_weights) if n in u.list_adapters()]
+            u.set_adapters([n for n, _ in mine], [w for _, w in mine])
+
+    def delete_adapters(self, adapter_names):
+        """diffusers' ``delete_adapters``: drops the named adapters from every UNet that has loaded them (unknown: ``ValueError``)."""
+        from ..components import lora as _lora
+
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        unets = self._lora_unets()
+        loaded = {n for _, u in unets for n in u.list_adapters()}
+        unknown = [n for n in names if n not in loaded]
+        if unknown:
+            raise _lora.LoraAdapterError(f"delete_adapters: no adapter named {unknown} is loaded (loaded: {self.get_list_adapters()})")
+        for _, u in unets:
+            mine = [n for n in names if n in u.list_adapters()]
+            if mine:
+                u.delete_adapters(mine)
+
+    def get_active_adapters(self):
+        """diffusers' ``get_active_adapters``: the adapters with a weight other than 0, in load order."""
+        out = []
+        for _, u in self._lora_unets():
+            out.extend(n for n in u.active_adapters() if n not in out)
+        return out
+
+    def get_list_adapters(self):
+        """diffusers' ``get_list_adapters``: ``{"unet": [...]}``, plus ``"gm_unet"`` when that UNet has any adapter."""
+        unet = getattr(self, "unet", None)
+        out = {"unet": unet.list_adapters() if unet is not None else []}
+        gm = getattr(self, "gm_unet", None)
+        if gm is not None and getattr(gm, "has_lora", False):
+            out["gm_unet"] = gm.list_adapters()
+        return out
+
+    def disable_lora(self):
+        """diffusers' ``disable_lora``: every adapter weight to 0, remembered; the launches stay (``UNet2DConditionModel.disable_lora``)."""
+        for _, u in self._lora_unets():
+            u.disable_lora()
+
+    def enable_lora(self):
+        """diffusers' ``enable_lora``: the weights ``disable_lora()`` remembered."""
+        for _, u in self._lora_unets():
+            u.enable_lora()
 
     def _apply_lora_scale(self, lora_scale):
         """``cross_attention_kwargs["scale"]`` of THIS call into the scale table of every UNet that carries an adapter, before the

@@ -742,6 +742,22 @@ int gmd_lora_update(const void* X, const void* Aw, const void* Bw, void* Y, int 
  * caller composes gmd_gemm_nt twice, gmd_scaled_add and gmd_geglu / gmd_geglu_interleaved). */
 int gmd_lora_geglu(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
                    int64_t ldx, int64_t ldy, int64_t ldf, const float* scales, int index, gmd_stream_t stream);
+/* SEVERAL LoRA adapters on one projection as ONE launch (added within ABI v14: two new entry points, no signature changed;
+ * csrc/lora.hip), GMD_BF16 / GMD_F16.  Operands, modes and checks of gmd_lora_update / gmd_lora_geglu, except:
+ *   Aw [Rp, K], Bw [N, Rp]: the adapters' factors side by side along the rank; the SUM of the ranks zero-padded to a multiple of 32,
+ *                           Rp in {32, 64, ..., 256}
+ *   colscales, index, ldc:  a float32 DEVICE table with row stride ldc >= Rp; the launch reads the Rp column scales of row `index`
+ *   T[m, j]  = round( colscales[index * ldc + j] * sum_k X[m, k] * Aw[j, k] )     float32 sum, the scale in float32, ONE rounding
+ *   Y[m, n] <- round( float(Y[m, n]) + sum_j T[m, j] * Bw[n, j] )                 float32 sum, one rounding on the store
+ *   GEGLU:    v, g as gmd_lora_geglu with U = sum_j T * Bw and no further scale
+ * A column whose sum over k is exactly 0 (every zero-padded column) contributes exactly 0 whatever its table entry holds.  Y (or F) is
+ * read and written once; the summation orders depend on k and j only, never on the grid; no atomics.
+ * GMD_ERR_INVALID also for Rp > 256, a NULL colscales, ldc < Rp, index < 0. */
+int gmd_lora_update_stacked(const void* X, const void* Aw, const void* Bw, void* Y, int dtype, int M, int K, int Rp, int N,
+                            int64_t ldx, int64_t ldy, int transposed, int batch, int tokens, int64_t strideY,
+                            const float* colscales, int index, int64_t ldc, gmd_stream_t stream);
+int gmd_lora_geglu_stacked(const void* X, const void* Aw, const void* Bw, const void* Y, void* F, int dtype, int M, int C, int Rp,
+                           int64_t ldx, int64_t ldy, int64_t ldf, const float* colscales, int index, int64_t ldc, gmd_stream_t stream);
 /* elementwise cast between F32 and BF16 */
 int gmd_cast(const void* in, int in_dtype, void* out, int out_dtype, int64_t n, gmd_stream_t stream);
 
